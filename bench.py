@@ -15,6 +15,7 @@ baseline (the oracle's C restatement of rfi.host, timed on this box's cores).
     python bench.py                      # 1 GPU
     python bench.py --gpus N             # starts N ranks itself (torch.distributed.run)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   # the same
+    python bench.py --dump-outputs DIR   # also write the last timed step's outputs (.npy)
 
 Parameters follow scripts/rfiflagtest.py of the reference: width 13, 11 sigma,
 4 windows, falloff 1.2, RandomState(seed=1) standard-normal real/imag.
@@ -42,6 +43,7 @@ PREHEAT_STEPS = 100  # x 0.45 ms: the clock ramp takes about 40 launches
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 ALGORITHMIC_BYTES_PER_SAMPLE = 9  # 8 B complex64 read + 1 B flag written
 CHECK_BASELINES = 512  # slice of the timed launch's output compared with the oracle
+DUMP_BYTES = 64_000_000  # --dump-outputs writes at most this much in all (.npy headers included)
 
 
 def synth_block(channels: int, baselines: int, seed: int) -> np.ndarray:
@@ -179,6 +181,22 @@ def check_against_oracle(vis_slice, mask, flags_slice, noise_slice) -> dict:
         "noise_equal": noise_equal,
         "flags_set_in_slice": int(np.count_nonzero(ref_flags)),
     }
+
+
+def dump_outputs(directory: str, outputs: dict, budget: int, suffix: str = "") -> None:
+    """Write `outputs` (name -> host array whose last axis is the baselines) as
+    ``directory/<name><suffix>.npy`` in float32. If the arrays would take more than `budget`
+    bytes, every one is cut to the same fixed, seeded sample of the baselines (sorted
+    indices from RandomState(0)), so that two builds can be compared output for output."""
+    baselines = next(iter(outputs.values())).shape[-1]
+    per_baseline = sum(4 * (a.size // a.shape[-1]) for a in outputs.values())
+    keep = min(baselines, (budget - 1024 * len(outputs)) // per_baseline)  # (1 KiB per header)
+    cols = np.arange(baselines)
+    if keep < baselines:
+        cols = np.sort(np.random.RandomState(0).choice(baselines, keep, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), a[..., cols].astype(np.float32))
 
 
 def measured_traffic(channels, baselines, use_flags, args):
@@ -415,7 +433,14 @@ def main() -> int:
                         help="also write the deviations slot (13 B/sample variant)")  # fmt: skip
     parser.add_argument("--sequence", action="store_true",
                         help="time the reference-shaped 5-kernel sequence instead of the fused kernel")  # fmt: skip
+    parser.add_argument("--dump-outputs", metavar="DIR",
+                        help="write what the last timed step computed (flags, noise and, with"
+                             " --keep-deviations, deviations; rfi_variant_* for the RFI-laden run) to"
+                             " DIR/<name>.npy as float32, at most 64 MB in all: a fixed, seeded"
+                             " sample of the baselines when the whole block does not fit")  # fmt: skip
     args = parser.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        parser.error("--steps must be at least 1 and --warmup not negative")
 
     # KSP_BENCH_FORCE_LAUNCH=1 takes the launcher route for N = 1 too (rehearsal of the
     # self-launch on a one-GPU box, together with KSP_BENCH_FORCE_DIST=1)
@@ -574,6 +599,19 @@ def main() -> int:
         kernel_s = [stop.time_since(start) for start, stop in kernel_events]
         return step_s, kernel_s or step_s
 
+    extras = world == 1 and not use_dist and not args.no_extras and not args.sequence
+
+    def dump(prefix: str) -> None:
+        """--dump-outputs: what a caller of the timed path receives from its last step
+        (`deviations` only when it is an output: asking the fused flagger for it otherwise
+        would change the kernel that runs)."""
+        if not args.dump_outputs:
+            return
+        names = ["flags", "noise"] + (["deviations"] if args.keep_deviations else [])
+        outputs = {prefix + name: fn.buffer(name).get(queue) for name in names}
+        budget = DUMP_BYTES // (world * (2 if extras else 1))  # every rank, and the RFI run
+        dump_outputs(args.dump_outputs, outputs, budget, f"_rank{rank}" if world > 1 else "")
+
     # From idle the device takes some tens of milliseconds of load to reach its sustained
     # clocks (launches right after set-up run up to 15 % longer). A continuously fed
     # flagger lives in the sustained state, so that is what the timed region measures;
@@ -598,6 +636,7 @@ def main() -> int:
         for _ in range(args.preheat - n_cold):
             step()
     elapsed, device_total = timed(args.steps, args.warmup, True)
+    dump("")
     step_s, kernel_s = sampled(min(args.steps, 50))
     stats = [elapsed, device_total / args.steps, float(np.mean(kernel_s)),
              float(np.max(step_s)), float(np.max(kernel_s)),
@@ -695,13 +734,13 @@ def main() -> int:
             "verified": verified,
         }  # fmt: skip
 
-    extras = world == 1 and not use_dist and not args.no_extras and not args.sequence
     if extras:
         # the same launch on RFI-laden input: SumThreshold's windows are summed and the
         # flagged bytes written (the plain input of the reference's script gives 0 flags)
         inject_rfi(vis, seed=3)
         fn.buffer("vis").set(queue, vis)
         r_elapsed, r_device = timed(args.steps, args.preheat + args.warmup, False)
+        dump("rfi_variant_")
         r_step, r_kernel = sampled(min(args.steps, 50))
         flags_out = fn.buffer("flags").get(queue)
         noise_out = fn.buffer("noise").get(queue)

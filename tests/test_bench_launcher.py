@@ -74,3 +74,42 @@ def test_inject_rfi_is_deterministic_and_sparse(bench):
     assert np.array_equal(a, b)
     strong = np.abs(a) > 40
     assert 0.04 < strong.mean() < 0.09
+
+
+def test_dump_outputs_whole_when_it_fits(bench, tmp_path):
+    import numpy as np
+
+    flags = (np.arange(6 * 10).reshape(6, 10) % 3 == 0).astype(np.uint8)
+    noise = np.linspace(0.5, 1.5, 10, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path), {"flags": flags, "noise": noise}, 1 << 20, "_rank1")
+    got = np.load(tmp_path / "flags_rank1.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, flags)
+    assert np.array_equal(np.load(tmp_path / "noise_rank1.npy"), noise)
+
+
+def test_dump_outputs_samples_the_same_baselines_within_budget(bench, tmp_path):
+    import numpy as np
+
+    channels, baselines, budget = 64, 5000, 300_000
+    rs = np.random.RandomState(5)
+    flags = (rs.random_sample((channels, baselines)) < 0.1).astype(np.uint8)
+    noise = rs.random_sample(baselines).astype(np.float32)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), {"flags": flags, "noise": noise}, budget)
+    files = sorted((tmp_path / "a").iterdir())
+    assert [f.name for f in files] == ["flags.npy", "noise.npy"]
+    assert sum(f.stat().st_size for f in files) <= budget
+    got_flags, got_noise = (np.load(f) for f in files)
+    assert got_flags.dtype == got_noise.dtype == np.float32
+    assert got_flags.shape[0] == channels and 0 < got_flags.shape[1] == got_noise.shape[0] < baselines
+    # the same columns of both outputs, and the same sample from run to run
+    cols = np.flatnonzero(np.isin(noise, got_noise))
+    assert np.array_equal(noise[cols], got_noise) and np.array_equal(flags[:, cols], got_flags)
+    for name in ("flags.npy", "noise.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name))
+
+
+def test_steps_must_be_positive(bench, monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.main()
