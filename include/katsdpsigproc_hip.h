@@ -122,7 +122,8 @@ int ksp_maskedsum_float(int device, void *stream, const void *in, const float *m
 /* background_median_filter (reference: rfi/background_median_filter.mako:200-220;
  * launch rfi/device.py:311-325). in: [C][stride] complex64 or float32 amplitudes;
  * out: [C][stride] float32 deviations; flags: [C] (CHANNEL) or [C][flags_stride]
- * (FULL) uint8, any non-zero value masks the sample. width must be odd, <= 63.
+ * (FULL) uint8, any non-zero value masks the sample. width must be odd, 3..255 (checked
+ * before any device call); 33..255 run the wide-window kernel (csrc/background_wide.h).
  * csplit: number of channel segments per baseline (the reference's tunable of the same
  * name, rfi/device.py:212-252), 0 = let the launcher choose. */
 int ksp_background_median_filter(int device, void *stream, const void *in, float *out,

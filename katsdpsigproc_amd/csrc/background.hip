@@ -22,6 +22,10 @@
 // prefix of the next -- about 21 min/med3/max per sample instead of the sorted window's
 // 12 compare/select pairs + 13 med3. A NaN visibility (which the host path skips, so
 // the window shrinks) sends the segment back through the sorted-window walk.
+//
+// Widths 33 to 255 go to background_wide_kernel (background_wide.h): a window spread over
+// eight lanes instead of one lane's registers.
+#include "background_wide.h"
 #include "median_merge.h"
 #include "median_window.h"
 
@@ -215,7 +219,11 @@ extern "C" int ksp_background_median_filter(int device, void *stream, const void
 {
     KSP_REQUIRE(in != nullptr && out != nullptr, "NULL buffer");
     KSP_REQUIRE(channels >= 0 && baselines >= 0 && stride >= baselines, "bad shape");
-    KSP_REQUIRE(width >= 3 && (width & 1), "width must be odd and >= 3");
+    if (width < 3 || width > ksp_bgwide::MAX_WIDTH || !(width & 1)) {
+        ksp_set_error("ksp_background_median_filter: width %d is not odd in 3..%d", width,
+                      ksp_bgwide::MAX_WIDTH);
+        return (int)hipErrorInvalidValue;
+    }
     KSP_REQUIRE(flags_mode >= KSP_FLAGS_NONE && flags_mode <= KSP_FLAGS_FULL, "bad flags_mode");
     KSP_REQUIRE(flags_mode == KSP_FLAGS_NONE || flags != nullptr, "flags buffer is NULL");
     KSP_REQUIRE(flags_mode != KSP_FLAGS_FULL || flags_stride >= baselines, "bad flags_stride");
@@ -227,6 +235,9 @@ extern "C" int ksp_background_median_filter(int device, void *stream, const void
     case W:                                                                                     \
         return launch_background<W>(s, in, out, flags, channels, baselines, stride, flags_stride, \
                                     is_amplitude, flags_mode, csplit)
+    if (width > 31)
+        return launch_background_wide_any(s, in, out, flags, channels, baselines, stride,
+                                          flags_stride, width, is_amplitude, flags_mode, csplit);
     switch (width) {
         KSP_BG(3);
         KSP_BG(5);
@@ -245,7 +256,7 @@ extern "C" int ksp_background_median_filter(int device, void *stream, const void
         KSP_BG(31);
     default:
         ksp_set_error("ksp_background_median_filter: width %d has no compiled kernel "
-                      "(available: odd 3..31)", width);
+                      "(available: odd 3..255)", width);
         return (int)hipErrorInvalidValue;
     }
 #undef KSP_BG

@@ -127,7 +127,8 @@ class BackgroundMedianFilterDeviceTemplate(AbstractBackgroundDeviceTemplate):
     context
         Context whose device will run the kernel
     width
-        Window width in channels: odd, 3 to 31
+        Window width in channels: odd, 3 to 255 (widths above 31 run a wide-window kernel
+        and cannot be fused into :class:`FusedFlaggerDevice`)
     is_amplitude
         Inputs are float32 amplitudes rather than complex64 visibilities
     use_flags
@@ -142,7 +143,7 @@ class BackgroundMedianFilterDeviceTemplate(AbstractBackgroundDeviceTemplate):
 
     host_class = host.BackgroundMedianFilterHost
     autotune_version = 5
-    SUPPORTED_WIDTHS = tuple(range(3, 32, 2))
+    SUPPORTED_WIDTHS = tuple(range(3, 256, 2))
 
     def __init__(self, context: AbstractContext, width: int, is_amplitude: bool = False,
                  use_flags: Union[BackgroundFlags, bool] = BackgroundFlags.NONE,
@@ -154,7 +155,7 @@ class BackgroundMedianFilterDeviceTemplate(AbstractBackgroundDeviceTemplate):
         if not isinstance(use_flags, BackgroundFlags):
             raise TypeError("use_flags must be an instance of BackgroundFlags or bool")
         if width not in self.SUPPORTED_WIDTHS:
-            raise ValueError(f"width {width} is not one of {self.SUPPORTED_WIDTHS}")
+            raise ValueError(f"width {width} is not an odd number in the range 3..255")
         self.context = context
         self.width = width
         self.is_amplitude = is_amplitude
