@@ -132,7 +132,8 @@ int ksp_background_median_filter(int device, void *stream, const void *in, float
                                  int csplit);
 
 /* madnz_t (reference: rfi/madnz_t.mako:72-87; launch rfi/device.py:594-607).
- * in: [B][stride] float32; noise[b] = float32(1.4826 * median(|x| : x != 0)). */
+ * in: [B][stride] float32; noise[b] = float32(1.4826 * median(|x| : x != 0)).
+ * channels 1..262144; more is rejected before any device call. */
 int ksp_madnz_t(int device, void *stream, const float *in, float *noise, int channels,
                 int baselines, int stride);
 

@@ -10,6 +10,9 @@
 // rfi/device.py:366), but the 16 channel phases of a workgroup make each pass a
 // set of contiguous 256-byte row reads that hit in L2 after the first pass.
 //
+// Rows of 16385..262144 channels take madnz_t_long_kernel (madnz_long.h): one
+// 1024-thread workgroup per baseline, radix select over three histogram passes.
+//
 // Numerics (reference rfi/host.py:157-163 on float32 input): numpy.median stays in
 // float32 -- even count -> float32(a + b) * 0.5 -- and the 1.4826 scale is applied
 // in float64; the float32 output is that float64 product rounded once.
@@ -19,6 +22,8 @@
 #include "rank.h"
 
 #define KSP_MAD_NORMAL 1.4826
+
+#include "madnz_long.h"
 
 template <int VT>
 __global__ __launch_bounds__(KSP_RANK_THREADS) void madnz_t_kernel(const float *__restrict__ in,
@@ -336,8 +341,34 @@ extern "C" int ksp_madnz_t(int device, void *stream, const float *in, float *noi
     KSP_REQUIRE(in != nullptr && noise != nullptr, "NULL buffer");
     KSP_REQUIRE(channels > 0 && baselines >= 0 && stride >= channels, "bad shape");
     if (baselines == 0) return 0;
+    if (channels > MADL_MAX_CHANNELS) {
+        ksp_set_error("ksp_madnz_t: %d channels outside the supported range 1..%d", channels,
+                      MADL_MAX_CHANNELS);
+        return (int)hipErrorInvalidValue;
+    }
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
+    if (channels > 64 * KSP_RANK_THREADS) {
+        // long rows (madnz_long.h): in LDS up to MADL_STAGE_MAX channels, else streamed
+        const int vec = (stride % 4 == 0) && ((uintptr_t)in % 16 == 0);
+        if (channels <= MADL_STAGE_MAX) {
+            static std::atomic<bool> attr_set[64];
+            if (device < 0 || device >= 64 || !attr_set[device].load(std::memory_order_acquire)) {
+                KSP_CHECK(hipFuncSetAttribute((const void *)madnz_t_long_kernel<true>,
+                                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              (int)(sizeof(unsigned) * MADL_STAGE_MAX)));
+                if (device >= 0 && device < 64) attr_set[device].store(true, std::memory_order_release);
+            }
+            const size_t lds = sizeof(unsigned) * 4 * (size_t)ksp_divup(channels, 4);
+            hipLaunchKernelGGL(madnz_t_long_kernel<true>, dim3(baselines), dim3(MADL_THREADS), lds,
+                               s, in, noise, channels, stride, vec);
+        } else {
+            hipLaunchKernelGGL(madnz_t_long_kernel<false>, dim3(baselines), dim3(MADL_THREADS), 0,
+                               s, in, noise, channels, stride, vec);
+        }
+        KSP_LAUNCH_CHECK();
+        return 0;
+    }
     if (channels > 1024 && channels <= 4096) {
         const int vec_ok = (stride % 4 == 0) && ((uintptr_t)in % 16 == 0);
         hipLaunchKernelGGL(madnz_t_wave_kernel, dim3(ksp_divup(baselines, 4)), dim3(256), 0, s, in,

@@ -362,6 +362,9 @@ class NoiseEstMADDevice(AbstractNoiseEstDevice):
     """
 
     transposed = False
+    #: Longest band for which ``method`` 1 (transpose + the baseline-major kernel) is used;
+    #: longer bands take the direct kernel whatever the tuning says.
+    MAX_TRANSPOSED_CHANNELS = 256 * 64
 
     def __init__(self, template: NoiseEstMADDeviceTemplate, command_queue: AbstractCommandQueue,
                  channels: int, baselines: int,
@@ -371,9 +374,8 @@ class NoiseEstMADDevice(AbstractNoiseEstDevice):
         self.kernel = template.kernel
         self.channels = channels
         self.baselines = baselines
-        # the baseline-major kernel holds a row in one workgroup's registers
         self.method = int(template.tuning.get("method", 0))
-        if channels > NoiseEstMADTDeviceTemplate.MAX_CHANNELS_SUPPORTED:
+        if channels > self.MAX_TRANSPOSED_CHANNELS:
             self.method = 0
         baselines_dim = accel.Dimension(baselines)
         self.slots["noise"] = accel.IOSlot((baselines_dim,), np.float32)
@@ -433,17 +435,19 @@ class NoiseEstMADTDeviceTemplate(AbstractNoiseEstDeviceTemplate):
     context
         Context whose device will run the kernel
     max_channels
-        Upper bound on channels per instance (at most 16384: a baseline is held in the
-        registers of one 256-work-item workgroup)
+        Upper bound on channels per instance (at most 262144, the reference's bound of
+        1024 x 256). Up to 16384 channels a baseline is held in the registers of a
+        wavefront or of one 256-work-item workgroup; longer rows go to a 1024-work-item
+        workgroup per baseline that selects the median by three histogram passes
     tuning
-        The kernel's geometry is fixed (a wavefront or a 256-thread workgroup per baseline):
+        The kernel's geometry is fixed (one wavefront or workgroup per baseline):
         ``wgsx`` of the reference is accepted without effect, any other key is a ``ValueError``
         (:func:`.tune.fixed_geometry`).
     """
 
     host_class = host.NoiseEstMADHost
     transposed = True
-    MAX_CHANNELS_SUPPORTED = 256 * 64
+    MAX_CHANNELS_SUPPORTED = 256 * 1024
     TUNING_KEYS = ("wgsx",)
 
     def __init__(self, context: AbstractContext, max_channels: int,
