@@ -108,7 +108,9 @@ int ksp_transpose(int device, void *stream, void *dst, const void *src, int in_r
 /* percentile5_float (reference: percentile.mako:115-140; percentile.py:193-209).
  * Per row, over columns [first_col, first_col + n_cols): out[0..4][row] =
  * min, max, sorted[(n-1)/4], sorted[3(n-1)/4], sorted[(n-1)/2] of |in|.
- * is_amplitude: in is float32 (positive); else complex64 and |.| is numpy's abs. */
+ * is_amplitude: in is float32 (positive); else complex64 and |.| is numpy's abs.
+ * n_cols 1..65536; more is rejected before any device call. Rows of 16385..65536 columns
+ * run the radix-select kernel (csrc/percentile_long.h), exact for signed float32 values. */
 int ksp_percentile5_float(int device, void *stream, const void *in, float *out, int rows,
                           int in_stride, int out_stride, int first_col, int n_cols,
                           int is_amplitude);

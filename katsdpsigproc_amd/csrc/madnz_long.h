@@ -27,7 +27,7 @@
 // counted lane of the wavefront hits the same bin (a constant row, a zero-heavy row),
 // which would otherwise serialise 64 ways on one bank.
 #pragma once
-#include "ksp_common.h"
+#include "hist_count.h"
 
 #define MADL_THREADS 1024
 #define MADL_WAVES (MADL_THREADS / KSP_WAVE)
@@ -64,21 +64,6 @@ __device__ __forceinline__ uint4 madl_load4(const float *row, int c, int channel
     return q;
 }
 
-// hist[bin] += 1 for every lane with `hit`; one atomic per wavefront when all those
-// lanes share the bin.
-__device__ __forceinline__ void madl_count(unsigned *hist, unsigned bin, bool hit)
-{
-    if (!hit) return;
-    const unsigned first = __builtin_amdgcn_readfirstlane(bin);
-    const unsigned long long active = __ballot(1);
-    if (__ballot(bin == first) == active) {
-        if (__lane_id() == __ffsll((unsigned long long)active) - 1)
-            atomicAdd(&hist[first], (unsigned)__popcll(active));
-    } else {
-        atomicAdd(&hist[bin], 1u);
-    }
-}
-
 // One histogram pass. PASS 1: bins = bits 30..20 of every non-zero pattern (and, when
 // STAGED, the patterns are stored to `stage`); PASS 2: bits 19..9 of those whose top 11
 // bits are `prefix`; PASS 3: bits 8..0 of those whose top 22 bits are `prefix`, returning
@@ -94,7 +79,7 @@ __device__ __forceinline__ unsigned madl_pass(const float *row, unsigned *stage,
     unsigned best = 0;
     auto one = [&](unsigned p) {
         // PASS 1: p >> 31 == 0 leaves out MADL_NONE
-        madl_count(hist, (p >> BSHIFT) & BMASK, p != 0 && (p >> MSHIFT) == prefix);
+        ksp_hist_count(hist, (p >> BSHIFT) & BMASK, p != 0 && (p >> MSHIFT) == prefix);
         if (PASS == 3) best = max(best, (p != 0 && p < lim) ? p : 0u);
     };
     auto quad = [&](uint4 q) {

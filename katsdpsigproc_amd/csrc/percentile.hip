@@ -182,10 +182,32 @@ __global__ __launch_bounds__(256) void percentile5_wave_kernel(const void *__res
     }
 }
 
+// Rows of 16385 .. 65536 columns: percentile5_long_kernel
+#include "percentile_long.h"
+
 template <bool IS_AMP>
 static int launch_percentile(hipStream_t s, const void *in, float *out, int rows, int in_stride,
                              int out_stride, int first_col, int n_cols)
 {
+    if (n_cols > 64 * KSP_RANK_THREADS) {
+        // one 1024-thread workgroup per row, VT values per thread (percentile_long.h); the
+        // same 16-byte load rule as the wave kernel
+        const int per16 = IS_AMP ? 4 : 2;
+        const int vec_ok = (in_stride % per16 == 0) && (first_col % per16 == 0) && ((uintptr_t)in % 16 == 0);
+        const int vt = ksp_divup(n_cols, P5L_THREADS);
+#define KSP_P5L(VT)                                                                             \
+    hipLaunchKernelGGL((percentile5_long_kernel<VT, IS_AMP>), dim3(rows), dim3(P5L_THREADS), 0, \
+                       s, in, out, rows, in_stride, out_stride, first_col, n_cols, vec_ok)
+        if (vt <= 32)
+            KSP_P5L(32);
+        else if (vt <= 48)
+            KSP_P5L(48);
+        else
+            KSP_P5L(64);
+#undef KSP_P5L
+        KSP_LAUNCH_CHECK();
+        return 0;
+    }
     if (n_cols > 1024 && n_cols <= 4096) {
         // 16-byte loads: every lane's first element 16-byte aligned
         const int per16 = IS_AMP ? 4 : 2;
@@ -236,6 +258,11 @@ extern "C" int ksp_percentile5_float(int device, void *stream, const void *in, f
     KSP_REQUIRE(first_col + n_cols <= in_stride, "column range exceeds the row stride");
     KSP_REQUIRE(out_stride >= rows, "out_stride smaller than rows");
     if (rows == 0) return 0;
+    if (n_cols > P5L_MAX_COLUMNS) {
+        ksp_set_error("ksp_percentile5_float: %d columns outside the supported range 1..%d", n_cols,
+                      P5L_MAX_COLUMNS);
+        return (int)hipErrorInvalidValue;
+    }
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
     return is_amplitude

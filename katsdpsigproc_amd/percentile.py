@@ -7,14 +7,16 @@ import numpy as np
 from . import accel, tune
 from .abc import AbstractCommandQueue, AbstractContext
 
-#: the gfx950 kernel keeps a row in registers: 256 work-items x up to 64 values
-MAX_COLUMNS_SUPPORTED = 256 * 64
+#: the gfx950 kernels keep a row in registers: up to 16384 columns in 256 work-items, longer
+#: rows (radix select) in 1024 work-items x up to 64 values
+MAX_COLUMNS_SUPPORTED = 1024 * 64
 
 
 class Percentile5Template:
     """Percentiles [0, 100, 25, 75, 50] of each row, "lower" element, no interpolation.
 
-    WARNING: assumes all values are positive (as the reference does).
+    WARNING: assumes all values are positive (as the reference does). Rows of more than
+    16384 columns are exact for signed float32 values too.
 
     Parameters
     ----------
@@ -25,9 +27,9 @@ class Percentile5Template:
     is_amplitude
         True: float32 amplitudes in; False: complex64 in, statistics of ``abs``
     tuning
-        The kernels' geometry is fixed (a wavefront or a 256-thread workgroup per row, chosen
-        from the number of columns): ``size``/``wgsy`` of the reference are accepted without
-        effect, any other key is a ``ValueError`` (:func:`.tune.fixed_geometry`).
+        The kernels' geometry is fixed (a wavefront, a 256-thread or a 1024-thread workgroup
+        per row, chosen from the number of columns): ``size``/``wgsy`` of the reference are
+        accepted without effect, any other key is a ``ValueError`` (:func:`.tune.fixed_geometry`).
     """
 
     TUNING_KEYS = ("size", "wgsy")
