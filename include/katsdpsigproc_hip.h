@@ -163,6 +163,16 @@ int ksp_threshold_sum(int device, void *stream, const float *deviations, const f
                       uint8_t *flags, int channels, int baselines, int stride, float n_sigma,
                       const float *scales, int n_windows, int flag_value, int vt);
 
+/* threshold_sum_cm: the same SumThreshold on channel-major data (no reference counterpart:
+ * the reference transposes deviations to [B][C] and flags back). deviations/flags:
+ * [C][stride], stride >= baselines, shared by both arrays; noise: [B]. Same thresholds,
+ * float64 sums and full-window rule, so flags equal ksp_threshold_sum's on the transposed
+ * array bit for bit. scales is a HOST pointer to n_windows floats (1..8). Every argument
+ * is checked before any device call; the launcher picks the channel segmentation. */
+int ksp_threshold_sum_cm(int device, void *stream, const float *deviations, const float *noise,
+                         uint8_t *flags, int channels, int baselines, int stride, float n_sigma,
+                         const float *scales, int n_windows, int flag_value);
+
 /* Fused single-pass flagger: the MI355X-native form of FlaggerDevice
  * (reference: rfi/device.py:1062-1166 composes background -> [transpose] ->
  * noise_est -> threshold -> [transpose]). One launch reads vis [C][vis_stride]

@@ -88,6 +88,10 @@ SIGNATURES = {
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
         POINTER(c_float), c_int, c_int, c_int,
     ],
+    "ksp_threshold_sum_cm": [
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
+        POINTER(c_float), c_int, c_int,
+    ],
     "ksp_flagger_fused": [
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
         c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, POINTER(c_double), c_int,

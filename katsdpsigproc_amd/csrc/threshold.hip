@@ -22,6 +22,10 @@
 // kernel's zero padding at the band edges is deliberately not reproduced.
 // When a baseline does not fit one chunk, chunks overlap by the reference's
 // EDGE = 2^n - n - 1 halo (rfi/device.py:848-850) and each writes only its core.
+//
+// threshold_sum_cm (threshold_cm.h): the same SumThreshold on channel-major deviations
+// ([C][B], no reference counterpart: the reference transposes first), lane <-> baseline,
+// the windows as a streaming pipeline along the channels. Same rules, same flags.
 #include "ksp_common.h"
 
 // ----------------------------------------------------------------------------
@@ -291,3 +295,6 @@ extern "C" int ksp_threshold_sum(int device, void *stream, const float *deviatio
     KSP_LAUNCH_CHECK();
     return 0;
 }
+
+// ----------------------------------------------------------------------------
+#include "threshold_cm.h"

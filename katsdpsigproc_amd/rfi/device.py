@@ -627,7 +627,8 @@ class ThresholdSimpleDevice(AbstractThresholdDevice):
 
 
 class ThresholdSumDeviceTemplate(AbstractThresholdDeviceTemplate):
-    """SumThreshold on baseline-major data (reference rfi/device.py:812-907).
+    """SumThreshold on baseline-major data (reference rfi/device.py:812-907), or on
+    channel-major data with ``transposed=False``.
 
     Follows :class:`host.ThresholdSumHost` exactly (float32 threshold chain, float64
     window sums over full windows only), where the reference kernel uses float32 sums
@@ -648,6 +649,12 @@ class ThresholdSumDeviceTemplate(AbstractThresholdDeviceTemplate):
         of 2048, 4096 or 8192 channels with a ``2**n_windows - n_windows - 1`` channel
         halo between chunks); 0 lets the launcher choose. ``wgs`` of the reference is
         fixed at 256. Default: autotuned and cached (:mod:`katsdpsigproc_amd.tune`).
+        Not used with ``transposed=False``: that launcher picks its own geometry.
+    transposed
+        ``True`` (default, the reference's only layout): `deviations` and `flags` are
+        baselines x channels. ``False``: channels x baselines, the layout the background
+        filter writes, so a flagger needs no transposes around this stage (no reference
+        counterpart). The flags are the same bit for bit.
     """
 
     host_class = host.ThresholdSumHost
@@ -655,14 +662,20 @@ class ThresholdSumDeviceTemplate(AbstractThresholdDeviceTemplate):
     autotune_version = 1
 
     def __init__(self, context: AbstractContext, n_windows: int = 4, flag_value: int = 1,
-                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+                 tuning: Optional[Mapping[str, Any]] = None, *,
+                 transposed: bool = True) -> None:  # fmt: skip
         if not 1 <= n_windows <= 8:
             raise ValueError("n_windows must be between 1 and 8")
         self.context = context
         self.n_windows = n_windows
         self.flag_value = flag_value
-        self._tuning = dict(tuning) if tuning is not None else None  # resolved on first use
-        self.kernel = context.native_kernel("ksp_threshold_sum")
+        self.transposed = bool(transposed)
+        if self.transposed:
+            self._tuning = dict(tuning) if tuning is not None else None  # resolved on first use
+            self.kernel = context.native_kernel("ksp_threshold_sum")
+        else:
+            self._tuning = dict(tuning) if tuning is not None else {}  # nothing to search
+            self.kernel = context.native_kernel("ksp_threshold_sum_cm")
 
     @property
     def tuning(self) -> Mapping[str, Any]:
@@ -710,9 +723,9 @@ class ThresholdSumDevice(AbstractThresholdDevice):
 
     .. rubric:: Slots
 
-    **deviations** : baselines x channels, float32
+    **deviations** : baselines x channels (channels x baselines if not transposed), float32
     **noise** : baselines, float32
-    **flags** : baselines x channels, uint8
+    **flags** : baselines x channels (channels x baselines if not transposed), uint8
     """
 
     host_class = host.ThresholdSumHost
@@ -735,14 +748,39 @@ class ThresholdSumDevice(AbstractThresholdDevice):
         self.scales = (ctypes_float_array(
             [np.float32(pow(threshold_falloff, -i)) for i in range(template.n_windows)]
         ))
-        # deviations and flags share the channel Dimension, hence the stride
-        dims = (baselines, accel.Dimension(channels))
-        self.slots["deviations"] = accel.IOSlot(dims, np.float32)
-        self.slots["noise"] = accel.IOSlot((baselines,), np.float32)
-        self.slots["flags"] = accel.IOSlot(dims, np.uint8)
+        self.transposed = template.transposed
+        if self.transposed:
+            # deviations and flags share the channel Dimension, hence the stride
+            dims = (baselines, accel.Dimension(channels))
+            self.slots["deviations"] = accel.IOSlot(dims, np.float32)
+            self.slots["noise"] = accel.IOSlot((baselines,), np.float32)
+            self.slots["flags"] = accel.IOSlot(dims, np.uint8)
+        else:
+            # as ThresholdSimpleDevice(transposed=False): one baseline Dimension throughout
+            dims = (channels, accel.Dimension(baselines))
+            self.slots["deviations"] = accel.IOSlot(dims, np.float32)
+            self.slots["noise"] = accel.IOSlot((dims[1],), np.float32)
+            self.slots["flags"] = accel.IOSlot(dims, np.uint8)
 
     def _run(self) -> None:
         deviations = self.buffer("deviations")
+        if not self.transposed:
+            self.command_queue.enqueue_kernel(
+                self.kernel,
+                [
+                    deviations.buffer,
+                    self.buffer("noise").buffer,
+                    self.buffer("flags").buffer,
+                    np.int32(self.channels),
+                    np.int32(self.baselines),
+                    np.int32(deviations.padded_shape[1]),
+                    np.float32(self.n_sigma),
+                    self.scales,
+                    np.int32(self.template.n_windows),
+                    np.int32(self.template.flag_value),
+                ],
+            )
+            return
         self.command_queue.enqueue_kernel(
             self.kernel,
             [
@@ -766,6 +804,7 @@ class ThresholdSumDevice(AbstractThresholdDevice):
             "threshold_falloff": self.threshold_falloff,
             "vt": self.template.tuning.get("vt", 0),
             "flag_value": self.template.flag_value,
+            "transposed": self.transposed,
             "channels": self.channels,
             "baselines": self.baselines,
         }
