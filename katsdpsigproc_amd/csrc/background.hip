@@ -21,7 +21,8 @@
 // WIDTH, and the window of an output is a sorted suffix of one block plus a sorted
 // prefix of the next -- about 21 min/med3/max per sample instead of the sorted window's
 // 12 compare/select pairs + 13 med3. A NaN visibility (which the host path skips, so
-// the window shrinks) sends the segment back through the sorted-window walk.
+// the window shrinks) or an infinite one (which takes no part in the host's window either)
+// sends the segment back through the sorted-window walk.
 //
 // Widths 33 to 255 go to background_wide_kernel (background_wide.h): a window spread over
 // eight lanes instead of one lane's registers.
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(256) void background_kernel(
 #pragma unroll
                 for (int k = 0; k < WIDTH; k++) {
                     cu[k] = nx[k];
-                    bad |= cu[k] != cu[k];
+                    bad |= !ksp_in_window(cu[k]);
                 }
                 fetch_rows(base + WIDTH, true);
                 float S[MergeMedian<64, WIDTH>::S_SIZE];
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(256) void background_kernel(
                 ksp_static_for<WIDTH>([&](auto t_) {
                     constexpr int t = decltype(t_)::value;
                     if constexpr (t >= 1) {
-                        bad |= nx[t - 1] != nx[t - 1];
+                        bad |= !ksp_in_window(nx[t - 1]);
                         if constexpr (t == 1)
                             P[0] = nx[0];
                         else
@@ -176,14 +177,14 @@ __global__ __launch_bounds__(256) void background_kernel(
             if (c < last) {          // wave-uniform
                 float leaving = ring[k];
                 asm("" : "+v"(leaving));  // opaque: do not carry the entry-time mask along
-                win.step(leaving, leaving == leaving, cur[k], cur[k] == cur[k]);
+                win.step(leaving, ksp_in_window(leaving), cur[k], ksp_in_window(cur[k]));
                 ring[k] = cur[k];
                 const int oc = c - H;  // output channel
                 if (oc >= c_begin) {   // wave-uniform; oc < c_end holds since c < last
                     float xc = ring[(k + WIDTH - H) % WIDTH];
                     asm("" : "+v"(xc));
                     float d = win.deviation(xc);
-                    d = (xc == xc) ? d : 0.0f;
+                    d = (d == d) ? d : 0.0f;  // NaN / masked centre, or no finite sample
                     if (active) out[(size_t)oc * stride + b] = d;
                 }
             }

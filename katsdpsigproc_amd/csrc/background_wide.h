@@ -12,7 +12,7 @@
 // last L (row_shr:1) -- so a step costs 3*S + O(1) vector instructions per lane and
 // about 3*N per sample: O(width), with no data-dependent control flow.
 //
-// Padding: samples that do not take part (flagged, NaN, outside the band) and the
+// Padding: samples that do not take part (flagged, NaN, infinite, outside the band) and the
 // N - width slots beyond the window are +-inf, with #(+inf) - #(-inf) in {0, 1}, as in
 // SortedWindow. N is even, so that difference is the parity of the number n of valid
 // samples: with n odd the median is s[N/2 - 1], with n even the mean of s[N/2 - 1] and
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void background_wide_kernel(
 #pragma unroll
         for (int t = 0; t < G; t++) {
             // remove: a leaving padding is taken from the +inf side when that side is ahead
-            const bool out_ok = vout[t] == vout[t];
+            const bool out_ok = ksp_in_window(vout[t]);
             const float vo = out_ok ? vout[t] : (odd ? pinf : ninf);
             odd = (odd == out_ok);
             float nxt = dpp<0x101>(pinf, s[0]);  // row_shl:1
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void background_wide_kernel(
             for (int j = 0; j < S - 1; j++) L[j] = s[j] < vo ? s[j] : s[j + 1];
             L[S - 1] = s[S - 1] < vo ? s[S - 1] : nxt;
             // insert: an entering padding goes to the side that is behind
-            const bool in_ok = vin[t] == vin[t];
+            const bool in_ok = ksp_in_window(vin[t]);
             const float vi = in_ok ? vin[t] : (odd ? ninf : pinf);
             odd = (odd == in_ok);
             float prv = dpp<0x111>(ninf, L[S - 1]);  // row_shr:1
@@ -188,8 +188,9 @@ __global__ __launch_bounds__(256) void background_wide_kernel(
         if (active && oc >= c_begin && oc < c_end) {
             // x - (lo + hi) / 2 in float64 with the host's roundings (the sum rounded, the
             // halving exact); for an odd count lo == hi and this is x - lo rounded once
-            const double dd = __fma_rn(-0.5, (double)m.x + (double)m.y, (double)x);
-            out[(size_t)oc * stride + b] = x == x ? (float)dd : 0.0f;
+            // (NaN: a masked centre, or no finite sample in the window)
+            const float d = (float)__fma_rn(-0.5, (double)m.x + (double)m.y, (double)x);
+            out[(size_t)oc * stride + b] = d == d ? d : 0.0f;
         }
         wave_sync();
         wslot += G;

@@ -290,7 +290,7 @@ __device__ __forceinline__ bool load_strip_fast(const FusedParams &p, float *lds
         lds[(2 * q) * LY::ROW + idx] = __builtin_nanf("");
         lds[(2 * q + 1) * LY::ROW + idx] = __builtin_nanf("");
     }
-    return umax > 0x7f800000u || flag_or != 0;
+    return umax >= 0x7f800000u || flag_or != 0;  // NaN or infinite amplitude
 }
 
 // ---------------------------------------------------------------------------------
@@ -300,9 +300,10 @@ __device__ __forceinline__ bool load_strip_fast(const FusedParams &p, float *lds
 // monotone, so order statistics can be located on the float32 values; the few samples
 // whose exact float64 value decides a result are recomputed on demand (exact_dev).
 // The LDS row holds NaN for every sample that must not take part (flagged, NaN input,
-// channels >= C); channels outside [0, 64 R) are never read.
-// General form: the samples are supplied by `amp_rel(i)`, -H <= i < R + H (NaN = takes
-// no part, including everything beyond the band).
+// channels >= C); channels outside [0, 64 R) are never read. An infinite amplitude stays
+// in the row: it takes no part in any window (as in the host path) but is its own centre.
+// General form: the samples are supplied by `amp_rel(i)`, -H <= i < R + H (NaN or +-inf =
+// takes no part in a window; NaN also beyond the band).
 template <int R, int WIDTH, class Src>
 __device__ __forceinline__ void median_phase_src(Src &&amp_rel, float (&dev)[R], float &dmax,
                                                  int *tiny = nullptr)
@@ -320,18 +321,18 @@ __device__ __forceinline__ void median_phase_src(Src &&amp_rel, float (&dev)[R],
         const int k = 2 * H + j;  // step number; channel (relative) H + j enters
         const float a = amp_rel(H + j);
         if (k < WIDTH) {
-            win.step_pad_out(a, a == a);  // what leaves is still the reset padding
+            win.step_pad_out(a, __builtin_fabsf(a) < win.pinf);  // what leaves is still the reset padding
         } else {
             float out = ring[k % WIDTH];
             asm("" : "+v"(out));  // opaque: do not carry the entry-time mask along
-            win.step(out, out == out, a, a == a);
+            win.step(out, __builtin_fabsf(out) < win.pinf, a, __builtin_fabsf(a) < win.pinf);
         }
         ring[k % WIDTH] = a;
         if (j >= 0) {
             float xc = ring[(k + WIDTH - H) % WIDTH];  // centre: relative channel j
             asm("" : "+v"(xc));
             float d = win.deviation(xc);
-            d = (xc == xc) ? d : 0.0f;
+            d = (d == d) ? d : 0.0f;  // NaN / masked centre, or no finite sample in the window
             dmax = __builtin_amdgcn_fmed3f(dmax, d, win.pinf);  // max, no canonicalise
             dev[j] = d;
         }
@@ -383,7 +384,7 @@ __device__ __forceinline__ double exact_dev(int c, Fetch &&fetch)
     int n = 0;
 #pragma unroll
     for (int k = 0; k < WIDTH; k++) {
-        const bool ok = a[k] == a[k];
+        const bool ok = __builtin_fabsf(a[k]) < pinf;  // finite: takes part
         n += ok;
         const float x = ok ? a[k] : pinf;
         // insert x into the sorted v[0 .. k)
@@ -408,7 +409,7 @@ __device__ __forceinline__ double exact_dev(int c, Fetch &&fetch)
     }
     if (!(centre == centre) || n == 0) return 0.0;
     const double med = (n & 1) ? (double)hi : ((double)lo + (double)hi) * 0.5;
-    return (double)centre - med;
+    return (double)centre - med;  // an infinite centre keeps its infinity
 }
 
 // ---------------------------------------------------------------------------------

@@ -58,7 +58,7 @@ __device__ __forceinline__ bool load_strip_long(const FusedParams &p, float *lds
             float a = p.is_amplitude ? raw[u].x : ksp_abs_c64(raw[u].x, raw[u].y);
             if (fl[u]) a = __builtin_nanf("");
             if (row < C) {
-                umax = max(umax, __float_as_uint(a));
+                umax = max(umax, __float_as_uint(a) & 0x7fffffffu);
                 myrow[long_index(row)] = a;
             }
         }
@@ -80,8 +80,8 @@ __device__ __forceinline__ bool load_strip_long(const FusedParams &p, float *lds
         }
     }
     for (int row = C + r0; row < 64 * runs; row += RSTEP) myrow[long_index(row)] = __builtin_nanf("");
-    // (negative amplitudes of an amplitude input sort above 0x80000000: not "masked")
-    return (umax & 0x7fffffffu) > 0x7f800000u;
+    // (|pattern|: a negative amplitude of an amplitude input must not hide a NaN or an inf)
+    return umax >= 0x7f800000u;  // masked, NaN or infinite
 }
 
 // Fast form for complex input and a whole strip of 4 baselines: two lanes per row, each
@@ -157,7 +157,7 @@ __device__ __forceinline__ bool load_strip_long_pairs(const FusedParams &p, floa
         row_a[long_index(row)] = __builtin_nanf("");
         row_b[long_index(row)] = __builtin_nanf("");
     }
-    return umax > 0x7f800000u || flag_or != 0;
+    return umax >= 0x7f800000u || flag_or != 0;  // NaN or infinite amplitude
 }
 
 // ---------------------------------------------------------------------------------

@@ -111,6 +111,11 @@ __device__ __forceinline__ unsigned long long ksp_ballot(bool x)
 }
 __device__ __forceinline__ bool ksp_any(bool x) { return __builtin_amdgcn_ballot_w64(x) != 0; }
 
+// Whether an amplitude takes part in a median window: the host path turns +-inf into NaN
+// before its rolling median (pandas BaseWindow._prep_values), so only finite samples do.
+// The centre's deviation still uses the raw value (inf - median = inf). One v_cmp_class.
+__device__ __forceinline__ bool ksp_in_window(float x) { return __builtin_isfinite(x); }
+
 // Two of them at once with packed float32 arithmetic (v_pk_fma_f32 / v_pk_mul_f32: two IEEE
 // operations per lane and instruction, same results): everything but the two reciprocals,
 // the two reciprocal square roots and the integer min/max is shared by the pair.

@@ -8,7 +8,7 @@
 // which is branch-free, data-independent, and keeps every array index static
 // after unrolling, so nothing spills to scratch.
 //
-// Samples that must not take part (flagged, NaN, or outside the band -- the host
+// Samples that must not take part (flagged, NaN, infinite, or outside the band -- the host
 // path masks them and uses min_periods=1, reference rfi/host.py:138-148) are
 // represented by +-infinity PADDING, split so that (#+inf - #-inf) is always 0 or
 // 1. The valid samples then sit centred in the sorted array: with an odd number of

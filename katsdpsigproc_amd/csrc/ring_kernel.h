@@ -550,9 +550,10 @@ __global__ __launch_bounds__(RING_THREADS) void flagger_ring_kernel(const FusedP
             if (lane == 63) exact &= ~last_odd;
         }
         // From here on the ring is not touched; the requests for the next strip stay in
-        // flight. A baseline with a NaN amplitude (NaN or infinite input) takes the general
-        // sorted-window median on amplitudes read again from global memory.
-        if (ksp_any(umax > 0x7f800000u)) {
+        // flight. A baseline with a NaN or infinite amplitude takes the general sorted-window
+        // median (infinities take no part in a window) on amplitudes read again from global
+        // memory.
+        if (ksp_any(umax >= 0x7f800000u)) {
             float a2[R + 2 * H];
             int c_first = lane * R - H;
             asm volatile("" : "+v"(c_first));  // (opaque: nothing of this path is hoisted out of the loop)

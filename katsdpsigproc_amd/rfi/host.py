@@ -63,9 +63,12 @@ class AbstractFlaggerHost(ABC):
 class BackgroundMedianFilterHost(AbstractBackgroundHost):
     """Amplitude minus its centred sliding median along channels.
 
-    The window is clipped at the band edges and skips flagged samples; an even number of
-    valid samples gives the mean of the middle two. Amplitudes are float32, the median
-    and the result float64 (as the reference, rfi/host.py:133-151).
+    The window is clipped at the band edges and skips flagged, NaN and infinite samples
+    (pandas turns +-inf into NaN before its rolling median); an even number of valid
+    samples gives the mean of the middle two. The deviation is taken from the unmasked
+    amplitude, so an infinite sample keeps ``inf - median``, and ``inf - NaN`` (no finite
+    sample in the window) becomes 0 like every other NaN. Amplitudes are float32, the
+    median and the result float64 (as the reference, rfi/host.py:133-151).
     """
 
     #: baselines processed per block, to bound the size of the window tensor
@@ -87,11 +90,12 @@ class BackgroundMedianFilterHost(AbstractBackgroundHost):
             if mask.ndim == 1:
                 mask = mask[:, np.newaxis]
             amp = np.where(np.broadcast_to(mask, amp.shape), np.nan, amp)
+        win_amp = np.where(np.isinf(amp), np.nan, amp)  # what the rolling median sees
         half = self.width // 2
         out = np.empty((channels, baselines), np.float64)
         pad = np.full((half, 1), np.nan)
         for start in range(0, baselines, self._BLOCK):
-            block = amp[:, start : start + self._BLOCK]
+            block = win_amp[:, start : start + self._BLOCK]
             padded = np.concatenate(
                 [np.broadcast_to(pad, (half, block.shape[1])), block,
                  np.broadcast_to(pad, (half, block.shape[1]))]
@@ -102,7 +106,8 @@ class BackgroundMedianFilterHost(AbstractBackgroundHost):
             lo = np.take_along_axis(ordered, np.maximum(count - 1, 0)[..., None] // 2, -1)[..., 0]
             hi = np.take_along_axis(ordered, (count // 2)[..., None], -1)[..., 0]
             median = (lo + hi) / 2.0
-            dev = block - median
+            with np.errstate(invalid="ignore"):
+                dev = amp[:, start : start + self._BLOCK] - median
             out[:, start : start + self._BLOCK] = np.where(np.isnan(dev), 0.0, dev)
         return out
 
@@ -111,8 +116,9 @@ class NoiseEstMADHost(AbstractNoiseEstHost):
     """``1.4826 * median(|d| : d != 0)`` per baseline.
 
     The median keeps the dtype of `deviations` (float32 in, float32 median -- even counts
-    average in float32), the scale is applied in float64 (reference rfi/host.py:157-163).
-    A baseline with no non-zero deviation gives NaN.
+    average in float32, odd counts take the middle value itself), the scale is applied in
+    float64 (reference rfi/host.py:157-163). A baseline with no non-zero deviation gives
+    NaN.
     """
 
     def __call__(self, deviations: np.ndarray) -> np.ndarray:
@@ -122,8 +128,8 @@ class NoiseEstMADHost(AbstractNoiseEstHost):
         cols = np.arange(mag.shape[1])
         lo = ordered[np.maximum(count - 1, 0) // 2, cols]
         hi = ordered[np.minimum(count // 2, mag.shape[0] - 1), cols]
-        with np.errstate(invalid="ignore"):
-            median = (lo + hi) / mag.dtype.type(2)
+        with np.errstate(invalid="ignore", over="ignore"):
+            median = np.where(count % 2 == 1, lo, (lo + hi) / mag.dtype.type(2))
         median = np.where(count > 0, median, np.nan)
         if np.any(count == 0):
             warnings.warn("baseline with no non-zero deviations", RuntimeWarning)

@@ -77,7 +77,11 @@ static double median_small(double *v, int n)
  *               masks the sample (host.py:143 astype(bool)).
  *   out: [C][B] float64 deviations, 0 where the sample is masked or NaN.
  * Window of output c is [c-H, c+H] clipped to the band; masked / NaN samples
- * are skipped (pandas min_periods=1).
+ * are skipped (pandas min_periods=1), and so are +-inf ones: pandas turns them
+ * into NaN before the rolling median (BaseWindow._prep_values). The deviation
+ * itself is taken from the raw amplitude, so an infinite sample keeps
+ * inf - median, and a sample whose window holds no finite value gets
+ * inf - NaN = NaN, which fillna(0) makes 0.
  */
 void oracle_background_median_filter(const void *vis, int is_amplitude,
                                      const uint8_t *flags, int flags_mode,
@@ -88,7 +92,7 @@ void oracle_background_median_filter(const void *vis, int is_amplitude,
 #pragma omp parallel
     {
         float *amp = (float *)malloc(sizeof(float) * (size_t)channels);
-        uint8_t *valid = (uint8_t *)malloc((size_t)channels);
+        uint8_t *valid = (uint8_t *)malloc((size_t)channels); /* 0 masked/NaN, 1 finite, 2 inf */
 #pragma omp for schedule(static)
         for (int b = 0; b < baselines; b++) {
             for (int c = 0; c < channels; c++) {
@@ -104,7 +108,7 @@ void oracle_background_median_filter(const void *vis, int is_amplitude,
                 else if (flags_mode == 2)
                     f = flags[idx] != 0;
                 amp[c] = a;
-                valid[c] = !f && !isnan(a);
+                valid[c] = (f || isnan(a)) ? 0 : isinf(a) ? 2 : 1;
             }
             for (int c = 0; c < channels; c++) {
                 size_t idx = (size_t)c * baselines + b;
@@ -113,7 +117,7 @@ void oracle_background_median_filter(const void *vis, int is_amplitude,
                 int lo = c - H < 0 ? 0 : c - H;
                 int hi = c + H >= channels ? channels - 1 : c + H;
                 for (int k = lo; k <= hi; k++)
-                    if (valid[k])
+                    if (valid[k] == 1)
                         win[n++] = (double)amp[k];
                 if (!valid[c] || n == 0)
                     out[idx] = 0.0;

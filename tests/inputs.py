@@ -5,6 +5,8 @@ same order of RandomState calls), so that the inputs need not be stored:
 ``np.random.RandomState`` legacy streams are frozen by NumPy's compatibility policy.
 """
 
+import os
+
 import numpy as np
 
 BACKGROUND_COLS = [0, 1, 17, 99, 100, 312]
@@ -169,3 +171,155 @@ def denormal_case(channels=4096):
             units[-10:, b] = edge[::-1]
             units[channels - 101, b], units[channels - 201, b] = 29, 23
     return (units * 2.0 ** -149).astype(np.float32)
+
+
+# Non-finite amplitudes (tests/golden/make_golden_nonfinite.py). Channel numbers of the
+# planted samples, per baseline of nonfinite_case(); golden slices are taken around them.
+NONFINITE_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                "rfi_host_nonfinite_golden.npz")
+NONFINITE_WIDTHS = (5, 13, 31, 63, 255)
+NONFINITE_MAD_CHANNELS = (4096, 4097, 20000, 20001)
+NONFINITE_CHANNELS = 4096
+NONFINITE_PLANTED = {
+    1: [1000, 1500, 2000, 2001],
+    2: list(range(500, 540)),
+    3: [800, 1200, 1600],
+    4: [0, NONFINITE_CHANNELS - 1],
+    5: [63, 64, 127, 128],
+    8: [700, 701, 1300, 2500],
+    9: [2222],
+    11: list(range(3000, 3010)) + list(range(3500, 3800)),
+}
+
+
+NONFINITE_AMP_PLANTED = {0: [100, 400], 1: list(range(200, 220)) + [600, 601, 602],
+                         2: [300, 301, 302, 700, 701], 3: list(range(400, 700))}
+
+
+def nonfinite_rows(planted=None, halo=2, limit=None):
+    """Sorted channel numbers within `halo` of a planted sample (runs: their two ends)."""
+    rows = set()
+    for chans in (planted or NONFINITE_PLANTED).values():
+        chans = sorted(chans)
+        ends = [c for i, c in enumerate(chans)
+                if i in (0, len(chans) - 1) or chans[i - 1] != c - 1 or chans[i + 1] != c + 1]
+        for c in ends:
+            rows.update(range(c - halo, c + halo + 1))
+    n = limit or NONFINITE_CHANNELS
+    return sorted(r for r in rows if 0 <= r < n)
+
+
+def nonfinite_case(channels=NONFINITE_CHANNELS, seed=21):
+    """complex64 [channels][12] of unit noise with one kind of non-finite input per baseline:
+    0 clean control; 1 isolated inf+0j, 0+inf*j, and inf+nan*j next to a NaN sample; 2 a run
+    of 40 samples of 3e38+3e38j (finite components, |z| overflows to inf); 3 the |z| overflow
+    boundary, 2.4e38+0j and 1.7e38+1.7e38j (finite) and 2.41e38+2.41e38j (inf); 4 inf at the
+    band edges; 5 inf on both sides of the lane boundaries 63/64 and 127/128; 6 all inf;
+    7 inf on every other channel; 8 infs that the input flags mask; 9 interference plus one
+    inf; 10 clean; 11 a run of 10 infs and one of 300 (longer than any window).
+    Returns (vis, input_flags [channels][12] uint8): 1/16 of the samples flagged with 2, and
+    every inf of baseline 8 with 1."""
+    rs = np.random.RandomState(seed)
+    shape = (channels, 12)
+    vis = complex_normal(rs, shape).astype(np.complex64)
+    inf = np.float32(np.inf)
+    vis[1000, 1] = complex(inf, 0)
+    vis[1500, 1] = complex(0, inf)
+    vis[2000, 1] = complex(inf, np.nan)
+    vis[2001, 1] = complex(np.nan, 0)
+    vis[500:540, 2] = complex(3e38, 3e38)
+    vis[800, 3] = complex(2.4e38, 0)
+    vis[1200, 3] = complex(1.7e38, 1.7e38)
+    vis[1600, 3] = complex(2.41e38, 2.41e38)
+    vis[[0, channels - 1], 4] = inf
+    vis[[63, 64, 127, 128], 5] = inf
+    vis[:, 6] = inf
+    vis[::2, 7] = inf
+    vis[[700, 701, 1300, 2500], 8] = inf
+    spikes = rs.random_sample(channels) < 1.0 / 16.0
+    rfi = (rs.random_sample(channels) * 20.0 + 50.0) * np.exp(rs.random_sample(channels) * 2j * np.pi)
+    vis[:, 9] += (spikes * rfi).astype(np.complex64)
+    vis[2222, 9] = inf
+    vis[3000:3010, 11] = inf
+    vis[3500:3800, 11] = inf
+    flags = (rs.random_sample(shape) < 1.0 / 16.0).astype(np.uint8) * 2
+    flags[[700, 701, 1300, 2500], 8] = 1
+    return vis, flags
+
+
+def nonfinite_amp_case(channels=1024, seed=22):
+    """float32 amplitudes [channels][5] (``amplitudes=True`` input, which may be negative):
+    0 isolated +inf and -inf; 1 runs of -inf (20 and 3); 2 negative finite amplitudes next
+    to +-inf; 3 a run of 300 +inf (longer than the widest window); 4 clean, with negatives.
+    Returns (amp, input_flags [channels][5] uint8)."""
+    rs = np.random.RandomState(seed)
+    amp = (rs.standard_normal((channels, 5)) + 3.0).astype(np.float32)
+    amp[100, 0], amp[400, 0] = np.inf, -np.inf
+    amp[200:220, 1] = -np.inf
+    amp[600:603, 1] = -np.inf
+    amp[300, 2], amp[301, 2], amp[302, 2] = -5.0, np.inf, -1e3
+    amp[700, 2], amp[701, 2] = -np.inf, -2.0
+    amp[400:700, 3] = np.inf
+    amp[::37, 4] *= -1.0
+    flags = (rs.random_sample(amp.shape) < 1.0 / 16.0).astype(np.uint8) * 2
+    return amp, flags
+
+
+def nonfinite_mad_case(channels, seed=23):
+    """float32 deviations [channels][6] for the MAD noise estimate: 0 a few +-inf among unit
+    noise; 1 more than half of them inf; 2 exactly half inf (the even-count midpoint is
+    (x + inf) / 2); 3 an odd count whose median |d| lies in (FLT_MAX/2, FLT_MAX]; 4 an even
+    count whose float32 midpoint sum overflows; 5 a quarter of the samples zero, +-inf mixed."""
+    rs = np.random.RandomState(seed)
+    dev = rs.standard_normal((channels, 6)).astype(np.float32)
+    idx = rs.permutation(channels)
+    dev[idx[:3], 0] = np.inf
+    dev[idx[3:5], 0] = -np.inf
+    dev[idx[: channels // 2 + 7], 1] = np.where(rs.random_sample(channels // 2 + 7) < 0.5, np.inf, -np.inf)
+    even = channels - (channels & 1)
+    dev[even:, 2] = 0.0
+    dev[idx[idx < even][: even // 2], 2] = -np.inf
+    big = rs.uniform(2.0e38, 3.2e38, channels).astype(np.float32) * np.where(rs.random_sample(channels) < 0.5, 1, -1).astype(np.float32)
+    odd = channels - 1 + (channels & 1)
+    dev[:, 3] = big
+    dev[odd:, 3] = 0.0
+    dev[:, 4] = np.abs(big)
+    dev[even:, 4] = 0.0
+    dev[idx[: channels // 4], 5] = 0.0
+    dev[idx[channels // 4 : channels // 4 + 9], 5] = np.inf
+    dev[idx[channels // 4 + 9 : channels // 4 + 12], 5] = -np.inf
+    return dev
+
+
+def nonfinite_threshold_case(channels=256, seed=24):
+    """float32 deviations [channels][8] and noise [8] for the thresholds: 0 control with
+    spikes; 1 one +inf; 2 one -inf next to a strong spike; 3 +inf and -inf two channels
+    apart (inside one window of 4); 4 +inf next to -inf; 5 noise +inf; 6 noise NaN; 7 a run of
+    6 infs."""
+    rs = np.random.RandomState(seed)
+    dev = rs.standard_normal((channels, 8)).astype(np.float32)
+    dev[rs.randint(0, channels, (6, 8)), np.arange(8)] += 40.0
+    dev[50, 1] = np.inf
+    dev[60, 2], dev[61, 2] = -np.inf, 30.0
+    dev[100, 3], dev[102, 3] = np.inf, -np.inf
+    dev[130, 4], dev[131, 4] = np.inf, -np.inf
+    dev[140, 5] = np.inf
+    dev[150, 6] = np.inf
+    dev[200:206, 7] = np.inf
+    noise = (0.9 + 0.2 * rs.random_sample(8)).astype(np.float32)
+    noise[5] = np.inf
+    noise[6] = np.nan
+    return dev, noise
+
+
+def nonfinite_golden():
+    return np.load(NONFINITE_GOLDEN, allow_pickle=False)
+
+
+def nonfinite_input(tag):
+    """(input, input flags, amplitudes, golden rows, channel-mode flag column) of a case."""
+    if tag == "cplx":
+        vis, flags = nonfinite_case()
+        return vis, flags, False, nonfinite_rows(), 8
+    amp, flags = nonfinite_amp_case()
+    return amp, flags, True, nonfinite_rows(NONFINITE_AMP_PLANTED, limit=amp.shape[0]), 3

@@ -441,9 +441,11 @@ class TestFused:
         np.testing.assert_array_equal(ref_flags, out["flags"])
 
     def test_full_band_mixed_strips(self, context, command_queue, oracle):
-        """4096 channels (the shape that takes the merging median): strips with a NaN
-        visibility fall back to the sorted-window path, strips with infinite samples
-        stay on the merging path; band edges of the first and last lane in both."""
+        """4096 channels (the shape that takes the merging median): strips with a NaN or an
+        infinite visibility fall back to the sorted-window path, where an infinity takes no
+        part in any window (as in the reference's rolling median) but keeps its own
+        deviation of inf; band edges of the first and last lane in both; a clean strip
+        stays on the merging median."""
         channels, baselines = 4096, 16
         vis = inputs.add_rfi(inputs.generate_data(channels, baselines, seed=41), seed=42)
         vis[100, 5] = np.nan
@@ -452,8 +454,12 @@ class TestFused:
         vis[200, 9] = np.inf
         vis[3, 10] = np.inf * 1j
         vis[4090, 11] = np.inf
+        vis[1000:1020, 11] = 3e38 + 3e38j  # |z| overflows: a run of infinities
         vis[:, 12] = 0
         out = run_fused(make_template(context), command_queue, vis, n_sigma=11.0)
+        assert np.isposinf(out["deviations"][[200, 3, 4090], [9, 10, 11]]).all()
+        assert (out["deviations"][1006:1014, 11] == 0).all()  # no finite sample in the window
+        assert np.isposinf(out["deviations"][[1000, 1005, 1014, 1019], 11]).all()
         with np.errstate(all="ignore"):
             ref_flags, ref_noise, ref_dev = oracle.flagger_full(vis, want_deviations=True)
         np.testing.assert_array_equal(ref_dev.astype(np.float32), out["deviations"])

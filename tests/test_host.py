@@ -1,6 +1,9 @@
 """The package's NumPy host classes (katsdpsigproc_amd.rfi.host) against golden vectors
 from the reference's host classes and against the reference's own known answers."""
 
+import contextlib
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -86,3 +89,59 @@ def test_flagger_golden(golden, name, mode):
     np.testing.assert_array_equal(
         flagger(vis, fl), unpack(golden[f"flagger_{name}_{mode}"], vis.shape)
     )
+
+
+# Non-finite input (tests/golden/make_golden_nonfinite.py), bit for bit.
+
+
+@pytest.fixture(scope="module")
+def nonfinite():
+    return inputs.nonfinite_golden()
+
+
+def digest(a):
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "f":
+        a = a + 0.0
+    return hashlib.sha256(a.tobytes()).hexdigest()
+
+
+@pytest.mark.parametrize("mode", ["none", "channel", "full"])
+@pytest.mark.parametrize("width", inputs.NONFINITE_WIDTHS)
+@pytest.mark.parametrize("tag", ["cplx", "amp"])
+def test_nonfinite_flagger_golden(nonfinite, tag, width, mode):
+    vis, in_flags, amplitudes, rows, chan_col = inputs.nonfinite_input(tag)
+    fl = {"none": None, "channel": in_flags[:, chan_col], "full": in_flags}[mode]
+    key = f"{tag}_w{width}_{mode}"
+    bg = host.BackgroundMedianFilterHost(width, amplitudes)
+    dev = bg(vis, fl)
+    if mode == "none":
+        np.testing.assert_array_equal(dev[rows], nonfinite[key + "_dev_rows"])
+    assert digest(dev) == str(nonfinite[key + "_dev_sha"])
+    with pytest.warns(RuntimeWarning) if tag == "cplx" else contextlib.nullcontext():
+        noise = host.NoiseEstMADHost()(dev)  # (the all-inf baseline has no non-zero deviation)
+    np.testing.assert_array_equal(noise, nonfinite[key + "_noise"])
+    flags = host.ThresholdSumHost(11.0)(dev, noise)
+    np.testing.assert_array_equal(flags, unpack(nonfinite[key + "_flags"], vis.shape))
+
+
+@pytest.mark.parametrize("channels", inputs.NONFINITE_MAD_CHANNELS)
+def test_nonfinite_mad_golden(nonfinite, channels):
+    noise = host.NoiseEstMADHost()(inputs.nonfinite_mad_case(channels))
+    np.testing.assert_array_equal(noise, nonfinite[f"mad_{channels}"])
+
+
+def test_mad_odd_count_near_flt_max():
+    """An odd count takes the middle value itself: (x + x) / 2 would overflow float32."""
+    dev = np.array([[1.0, 2e38, 3e38]], np.float32).T
+    np.testing.assert_array_equal(host.NoiseEstMADHost()(dev), [float(np.float32(2e38)) * 1.4826])
+    assert host.ThresholdSimpleHost(1.0)(dev, host.NoiseEstMADHost()(dev))[2, 0] == 1
+
+
+def test_nonfinite_threshold_golden(nonfinite):
+    dev, noise = inputs.nonfinite_threshold_case()
+    np.testing.assert_array_equal(host.ThresholdSimpleHost(11.0)(dev, noise),
+                                  unpack(nonfinite["threshold_simple"], dev.shape))  # fmt: skip
+    for n_windows in range(1, 9):
+        fl = host.ThresholdSumHost(11.0, n_windows=n_windows)(dev, noise)
+        np.testing.assert_array_equal(fl, unpack(nonfinite[f"threshold_sum_w{n_windows}"], dev.shape))

@@ -199,3 +199,65 @@ def test_percentile5_matches_numpy():
         lo, hi = rng if rng else (0, ary.shape[1])
         expected = np.percentile(ary[:, lo:hi], [0, 100, 25, 75, 50], axis=1, method="lower")
         np.testing.assert_array_equal(expected.astype(np.float32), oracle.percentile5(ary, rng))
+
+
+# ---------------------------------------------------------------------------------------
+# Non-finite input (tests/golden/make_golden_nonfinite.py): +-inf amplitudes take no part
+# in any window, their own deviation is inf - median (0 when no finite sample is left).
+
+
+@pytest.fixture(scope="module")
+def nonfinite():
+    return inputs.nonfinite_golden()
+
+
+@pytest.mark.parametrize("mode", ["none", "channel", "full"])
+@pytest.mark.parametrize("width", inputs.NONFINITE_WIDTHS)
+@pytest.mark.parametrize("tag", ["cplx", "amp"])
+def test_nonfinite_flagger_golden(nonfinite, tag, width, mode):
+    vis, in_flags, amplitudes, rows, chan_col = inputs.nonfinite_input(tag)
+    fl = {"none": None, "channel": in_flags[:, chan_col], "full": in_flags}[mode]
+    key = f"{tag}_w{width}_{mode}"
+    flags, noise, dev = oracle.flagger_full(vis, fl, width=width, amplitudes=amplitudes,
+                                            want_deviations=True)  # fmt: skip
+    if mode == "none":
+        np.testing.assert_array_equal(dev[rows], nonfinite[key + "_dev_rows"])
+    assert digest(dev) == str(nonfinite[key + "_dev_sha"])
+    np.testing.assert_array_equal(noise, nonfinite[key + "_noise"])
+    np.testing.assert_array_equal(flags, unpack(nonfinite[key + "_flags"], vis.shape))
+    # the background class alone gives the same deviations
+    alone = oracle.BackgroundMedianFilterHost(width, amplitudes)(vis, fl)
+    assert digest(alone) == str(nonfinite[key + "_dev_sha"])
+
+
+def test_nonfinite_golden_has_teeth(nonfinite):
+    """The fixture holds what the issue describes: infinite deviations survive, a window
+    of infinities alone gives 0, an all-inf baseline has NaN noise and no flags."""
+    dev_rows = nonfinite["cplx_w13_none_dev_rows"]
+    rows = inputs.nonfinite_rows()
+    assert np.isposinf(dev_rows[rows.index(1000), 1])
+    assert np.isposinf(dev_rows[rows.index(500), 2]) and dev_rows[rows.index(539), 2] == np.inf
+    noise = nonfinite["cplx_w13_none_noise"]
+    assert np.isnan(noise[6]) and np.isposinf(noise[7])
+    flags = unpack(nonfinite["cplx_w13_none_flags"], (inputs.NONFINITE_CHANNELS, 12))
+    assert not flags[:, 6].any() and not flags[:, 7].any() and flags[:, 9].any()
+    amp_rows = nonfinite["amp_w5_none_dev_rows"]
+    assert np.isneginf(amp_rows).any() and np.isposinf(amp_rows).any()
+
+
+@pytest.mark.parametrize("channels", inputs.NONFINITE_MAD_CHANNELS)
+def test_nonfinite_mad_golden(nonfinite, channels):
+    dev = inputs.nonfinite_mad_case(channels)
+    noise = oracle.NoiseEstMADHost()(dev)
+    np.testing.assert_array_equal(noise, nonfinite[f"mad_{channels}"])
+    assert np.isposinf(noise[[1, 2, 4]]).all() and np.isfinite(noise[[0, 3, 5]]).all()
+    assert noise[3] > np.finfo(np.float32).max / 2 * 1.4826  # the odd count's middle value
+
+
+def test_nonfinite_threshold_golden(nonfinite):
+    dev, noise = inputs.nonfinite_threshold_case()
+    np.testing.assert_array_equal(oracle.ThresholdSimpleHost(11.0)(dev, noise),
+                                  unpack(nonfinite["threshold_simple"], dev.shape))  # fmt: skip
+    for n_windows in range(1, 9):
+        fl = oracle.ThresholdSumHost(11.0, n_windows=n_windows)(dev, noise)
+        np.testing.assert_array_equal(fl, unpack(nonfinite[f"threshold_sum_w{n_windows}"], dev.shape))
