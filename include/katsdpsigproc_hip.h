@@ -286,6 +286,43 @@ int ksp_fft_plan_destroy(int device, void *plan);
 int ksp_fft_exec(int device, void *stream, void *plan, int type, void *src, void *dest,
                  void *work_area, int inverse);
 
+/* ---- Two-dimensional SumThreshold flagger (reference rfi/twodflag.py:236-482) ----
+ * Parameters as the reference's SumThresholdFlagger._get_flags hands them to
+ * _get_flags_impl, already conditioned on the host: windows clipped (and, for frequency,
+ * scaled and made unique), chunk ends from numpy.linspace, spike_width_freq divided by
+ * average_freq. tf_* = rho ** log2(window); threshold_scale = outlier_nsigma * MAD_NORMAL;
+ * reject_scale = MAD_NORMAL * background_reject (all float64, as numba computes them).
+ * Limits: n_time 1..KSP_TDF_MAX_TIME, n_freq 1..KSP_TDF_MAX_FREQ, 1..32 windows per axis,
+ * 1..KSP_TDF_MAX_CHUNKS frequency chunks, background_iterations 0..64, box-filter radii
+ * up to KSP_TDF_MAX_RADIUS. */
+#define KSP_TDF_MAX_TIME 4096
+#define KSP_TDF_MAX_FREQ 65536
+#define KSP_TDF_MAX_WINDOWS 32
+#define KSP_TDF_MAX_CHUNKS 512
+#define KSP_TDF_MAX_RADIUS 2047
+typedef struct ksp_twodflag_params {
+    int n_time, n_freq, average_freq, is_amplitude;
+    int n_windows_time, n_windows_freq;
+    int windows_time[KSP_TDF_MAX_WINDOWS], windows_freq[KSP_TDF_MAX_WINDOWS];
+    double tf_time[KSP_TDF_MAX_WINDOWS], tf_freq[KSP_TDF_MAX_WINDOWS];
+    int n_chunks;
+    int chunk_ends[KSP_TDF_MAX_CHUNKS + 1];
+    int background_iterations, time_extend, freq_extend;
+    double spike_width_time, spike_width_freq;
+    double threshold_scale, reject_scale, flag_all_time_frac, flag_all_freq_frac;
+} ksp_twodflag_params;
+/* ksp_twodflag_workspace: bytes of device workspace for batches of `batch` baselines.
+ * ksp_twodflag: flags for baselines [bl0, bl0 + batch) of data[n_time][n_freq][n_bl]
+ *   (complex64, or float32 if is_amplitude), in_flags and out_flags uint8 of the same
+ *   layout; stride_t and stride_f are the element strides of the time and channel axes
+ *   (baselines contiguous). out = reference get_flags(...) for those baselines. Every
+ *   argument is checked before any device call. */
+int ksp_twodflag_workspace(const ksp_twodflag_params *params, int batch, size_t *bytes);
+int ksp_twodflag(int device, void *stream, const void *data, const uint8_t *in_flags,
+                 uint8_t *out_flags, int n_bl, long long stride_t, long long stride_f, int bl0,
+                 int batch, const ksp_twodflag_params *params, void *workspace,
+                 size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,25 @@ class DeviceProps(ctypes.Structure):
 
 _SIZE3 = c_size_t * 3
 
+TDF_MAX_WINDOWS = 32
+TDF_MAX_CHUNKS = 512
+
+
+class TwodflagParams(ctypes.Structure):
+    """Mirror of ``ksp_twodflag_params``."""
+
+    _fields_ = [
+        ("n_time", c_int), ("n_freq", c_int), ("average_freq", c_int), ("is_amplitude", c_int),
+        ("n_windows_time", c_int), ("n_windows_freq", c_int),
+        ("windows_time", c_int * TDF_MAX_WINDOWS), ("windows_freq", c_int * TDF_MAX_WINDOWS),
+        ("tf_time", c_double * TDF_MAX_WINDOWS), ("tf_freq", c_double * TDF_MAX_WINDOWS),
+        ("n_chunks", c_int), ("chunk_ends", c_int * (TDF_MAX_CHUNKS + 1)),
+        ("background_iterations", c_int), ("time_extend", c_int), ("freq_extend", c_int),
+        ("spike_width_time", c_double), ("spike_width_freq", c_double),
+        ("threshold_scale", c_double), ("reject_scale", c_double),
+        ("flag_all_time_frac", c_double), ("flag_all_freq_frac", c_double),
+    ]  # fmt: skip
+
 # name -> argtypes; every function returns int (0 = success) unless listed in _OTHER
 SIGNATURES = {
     "ksp_device_count": [POINTER(c_int)],
@@ -112,6 +131,11 @@ SIGNATURES = {
     ],
     "ksp_fft_plan_destroy": [c_int, c_void_p],
     "ksp_fft_exec": [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int],
+    "ksp_twodflag_workspace": [POINTER(TwodflagParams), c_int, POINTER(c_size_t)],
+    "ksp_twodflag": [
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, ctypes.c_longlong,
+        c_int, c_int, POINTER(TwodflagParams), c_void_p, c_size_t,
+    ],
     "ksp_launch_function": [
         c_int, c_void_p, c_void_p, POINTER(ctypes.c_uint), POINTER(ctypes.c_uint), ctypes.c_uint,
         POINTER(c_void_p),
@@ -189,6 +213,6 @@ def call(name: str, *args) -> int:
 
 
 __all__ = [
-    "ABI_VERSION", "DeviceProps", "LIB_PATH", "SIGNATURES", "byref", "call", "declared_symbols",
+    "ABI_VERSION", "DeviceProps", "TwodflagParams", "LIB_PATH", "SIGNATURES", "byref", "call", "declared_symbols",
     "last_error", "load",
 ]  # fmt: skip
