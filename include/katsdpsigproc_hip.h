@@ -318,6 +318,28 @@ typedef struct ksp_twodflag_params {
  *   (baselines contiguous). out = reference get_flags(...) for those baselines. Every
  *   argument is checked before any device call. */
 int ksp_twodflag_workspace(const ksp_twodflag_params *params, int batch, size_t *bytes);
+/* Byte offsets within the workspace of the temporaries a ksp_twodflag call leaves there.
+ * After the call returns (and its stream has drained), they hold the stages of that call's
+ * batch, baseline-major: B = batch, T = n_time, A = averaged channels, F = n_freq;
+ * float32 where named so, else uint8 0/1.
+ *   spec_flags [B][A]            median spectrum flags (no unflagged time)
+ *   spec_background [B][A]       float32, background of the median spectrum
+ *   spec_residual [B][A]         float32, median spectrum - its background
+ *   spec_st [B][A]               SumThreshold flags of the spectrum
+ *   flags [B][T][A]              averaged input flags | spec_st
+ *   background [B][T][A]         float32, 2-D background
+ *   residual [B][T][A]           float32, averaged data - 2-D background
+ *   time_flags, freq_flags [B][T][A]   SumThreshold along time / along frequency
+ *   combined [B][T][A]           spec_st | time | frequency flags, smeared in time
+ *   row_flags [B][T][F]          combined, un-averaged and smeared in frequency
+ *   row_all [B][T], col_all [B][F]     whole-time / whole-channel flags
+ * ksp_twodflag_layout checks its arguments as ksp_twodflag_workspace does; host only. */
+typedef struct ksp_twodflag_offsets {
+    size_t spec_flags, spec_background, spec_residual, spec_st;
+    size_t flags, background, residual, time_flags, freq_flags, combined;
+    size_t row_flags, row_all, col_all;
+} ksp_twodflag_offsets;
+int ksp_twodflag_layout(const ksp_twodflag_params *params, int batch, ksp_twodflag_offsets *out);
 int ksp_twodflag(int device, void *stream, const void *data, const uint8_t *in_flags,
                  uint8_t *out_flags, int n_bl, long long stride_t, long long stride_f, int bl0,
                  int batch, const ksp_twodflag_params *params, void *workspace,

@@ -57,6 +57,16 @@ class TwodflagParams(ctypes.Structure):
         ("flag_all_time_frac", c_double), ("flag_all_freq_frac", c_double),
     ]  # fmt: skip
 
+
+class TwodflagOffsets(ctypes.Structure):
+    """Mirror of ``ksp_twodflag_offsets``: workspace byte offsets of the stages."""
+
+    _fields_ = [(name, c_size_t) for name in (
+        "spec_flags", "spec_background", "spec_residual", "spec_st", "flags", "background",
+        "residual", "time_flags", "freq_flags", "combined", "row_flags", "row_all", "col_all",
+    )]  # fmt: skip
+
+
 # name -> argtypes; every function returns int (0 = success) unless listed in _OTHER
 SIGNATURES = {
     "ksp_device_count": [POINTER(c_int)],
@@ -132,6 +142,7 @@ SIGNATURES = {
     "ksp_fft_plan_destroy": [c_int, c_void_p],
     "ksp_fft_exec": [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int],
     "ksp_twodflag_workspace": [POINTER(TwodflagParams), c_int, POINTER(c_size_t)],
+    "ksp_twodflag_layout": [POINTER(TwodflagParams), c_int, POINTER(TwodflagOffsets)],
     "ksp_twodflag": [
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, ctypes.c_longlong,
         c_int, c_int, POINTER(TwodflagParams), c_void_p, c_size_t,
@@ -213,6 +224,6 @@ def call(name: str, *args) -> int:
 
 
 __all__ = [
-    "ABI_VERSION", "DeviceProps", "TwodflagParams", "LIB_PATH", "SIGNATURES", "byref", "call", "declared_symbols",
+    "ABI_VERSION", "DeviceProps", "TwodflagOffsets", "TwodflagParams", "LIB_PATH", "SIGNATURES", "byref", "call", "declared_symbols",
     "last_error", "load",
 ]  # fmt: skip

@@ -711,6 +711,30 @@ extern "C" int ksp_twodflag_workspace(const ksp_twodflag_params *params, int bat
     return 0;
 }
 
+extern "C" int ksp_twodflag_layout(const ksp_twodflag_params *params, int batch,
+                                   ksp_twodflag_offsets *out)
+{
+    KSP_REQUIRE(out != nullptr, "NULL out");
+    if (int rc = tdf_check(params)) return rc;
+    KSP_REQUIRE(batch >= 1, "batch < 1");
+    const TdfLayout L = tdf_layout(params, batch);
+    // where ksp_twodflag leaves each stage (the buffers named in its body)
+    out->spec_flags = L.specflg;
+    out->spec_background = L.specO;
+    out->spec_residual = L.spec;
+    out->spec_st = L.specst;
+    out->flags = L.flg;
+    out->background = L.O;
+    out->residual = L.avg;
+    out->time_flags = L.tfl;
+    out->freq_flags = L.ffl;
+    out->combined = L.work;
+    out->row_flags = L.rowfl;
+    out->row_all = L.rowall;
+    out->col_all = L.colall;
+    return 0;
+}
+
 extern "C" int ksp_twodflag(int device, void *stream, const void *data, const uint8_t *in_flags,
                             uint8_t *out_flags, int n_bl, long long stride_t, long long stride_f,
                             int bl0, int batch, const ksp_twodflag_params *params,

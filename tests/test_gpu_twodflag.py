@@ -198,3 +198,9 @@ def test_large_block_matches_subset(context):
                             np.ascontiguousarray(flags[..., sample]))  # fmt: skip
     np.testing.assert_array_equal(out[..., sample], sub)
     assert out[..., sample].any()
+    # and the sampled baselines are what the NumPy oracle computes for them
+    from oracle import twodflag_oracle as oracle
+
+    expected, _ = oracle.flag(np.ascontiguousarray(data[..., sample]),
+                              np.ascontiguousarray(flags[..., sample]))  # fmt: skip
+    np.testing.assert_array_equal(out[..., sample], expected)
