@@ -345,6 +345,26 @@ int ksp_twodflag(int device, void *stream, const void *data, const uint8_t *in_f
                  int batch, const ksp_twodflag_params *params, void *workspace,
                  size_t workspace_bytes);
 
+/* ---- masked_gaussian_filter (reference rfi/twodflag.py:254-400) ----
+ * Images [images][rows][cols] of float32 (itemsize 4) or float64 (itemsize 8); data, flags
+ * (uint8, non-zero = flagged) and out share image_stride and row_stride, in elements
+ * (columns contiguous). r0 / r1: box radius along axis 0 / axis 1 (0 = not filtered along
+ * that axis); divisor0 / divisor1: (2 r + 1) ** passes as numba computes it, by squaring
+ * and multiplying in the data's type (any positive value where the radius is 0).
+ * out = NaN where the filtered weight is 0, else filtered masked data / filtered weight,
+ * bit for bit the reference's result. out may be the same buffer as data.
+ * Limits: rows, cols 1..65536; passes 1..8; radii 0..2047; with passes = 1 a radius may
+ * not exceed the length of its axis. Every argument is checked before any device call.
+ * ksp_masked_filter_workspace: bytes of device workspace for batches of `batch` images.
+ * ksp_masked_filter: filters images [image0, image0 + batch). */
+int ksp_masked_filter_workspace(int rows, int cols, int batch, int r0, int r1, int passes,
+                                int itemsize, size_t *bytes);
+int ksp_masked_filter(int device, void *stream, const void *data, const uint8_t *flags, void *out,
+                      int rows, int cols, int images, long long image_stride,
+                      long long row_stride, int image0, int batch, int r0, int r1, int passes,
+                      double divisor0, double divisor1, int itemsize, void *workspace,
+                      size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,14 @@ SIGNATURES = {
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, ctypes.c_longlong,
         c_int, c_int, POINTER(TwodflagParams), c_void_p, c_size_t,
     ],
+    "ksp_masked_filter_workspace": [
+        c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t),
+    ],
+    "ksp_masked_filter": [
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_longlong,
+        ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_int,
+        c_void_p, c_size_t,
+    ],
     "ksp_launch_function": [
         c_int, c_void_p, c_void_p, POINTER(ctypes.c_uint), POINTER(ctypes.c_uint), ctypes.c_uint,
         POINTER(c_void_p),

@@ -6,10 +6,15 @@ flags (see DESIGN.md section 9 for the arithmetic followed), computed by the HIP
 ``csrc/twodflag.hip``. :class:`SumThresholdFlaggerDeviceTemplate` is the device
 :class:`~katsdpsigproc_amd.accel.Operation` behind it, for pipelines that keep the block on
 the device.
+
+:func:`masked_gaussian_filter` is the module's other public name (reference
+rfi/twodflag.py:360-400), bit-identical as well, on the kernels of ``csrc/masked_filter.hip``;
+:class:`MaskedGaussianFilterTemplate` is its device operation.
 """
 
 import ctypes
-from typing import Any, Mapping, Optional
+import math
+from typing import Any, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -25,6 +30,10 @@ MAX_CHUNKS = _lib.TDF_MAX_CHUNKS
 MAX_ITERATIONS = 64
 #: device workspace per batch of baselines, unless a batch size is given
 DEFAULT_WORKSPACE_BYTES = 2 << 30
+#: limits of the masked Gaussian filter
+MAX_FILTER_DIM = 65536
+MAX_FILTER_PASSES = 8
+MAX_FILTER_RADIUS = 2047
 
 
 def _as_min_dtype(value):
@@ -272,3 +281,211 @@ class SumThresholdFlagger(_Conditioned):
         op()
         out = op.buffer("flags").get(self._queue)
         return out.view(np.bool_)
+
+
+def _filter_radius(sigma: float, passes: int) -> int:
+    """Box radius for `sigma` (reference ``_box_gaussian_filter``), in float64."""
+    return int(0.5 * math.sqrt(12.0 * float(sigma) ** 2 / passes + 1))
+
+
+def _filter_divisor(radius: int, passes: int, dtype) -> float:
+    """``dtype(2 * radius + 1) ** passes`` as numba computes it (``int_power_impl``): by
+    squaring and multiplying, every product rounded to `dtype`."""
+    scalar = np.dtype(dtype).type
+    result, base, e = scalar(1), scalar(2 * radius + 1), int(passes)
+    with np.errstate(over="ignore"):  # (the last squaring is not used)
+        while e:
+            if e & 1:
+                result = scalar(result * base)
+            base = scalar(base * base)
+            e >>= 1
+    return float(result)
+
+
+def _check_passes(passes) -> None:
+    if isinstance(passes, (bool, np.bool_)) or not isinstance(passes, (int, np.integer)):
+        raise TypeError("passes must be an integer")
+    if not 1 <= passes <= MAX_FILTER_PASSES:
+        raise ValueError(f"passes must be in 1..{MAX_FILTER_PASSES}")
+
+
+def _filter_radii(rows: int, cols: int, sigma, passes: int):
+    """Checks the image shape and `sigma` against the limits; returns (sigma, radii)."""
+    if not (1 <= rows <= MAX_FILTER_DIM and 1 <= cols <= MAX_FILTER_DIM):
+        raise ValueError(f"rows and cols must be in 1..{MAX_FILTER_DIM}")
+    sigma = tuple(float(s) for s in sigma)
+    if len(sigma) != 2:
+        raise ValueError("sigma has wrong number of elements")
+    if not all(math.isfinite(s) for s in sigma):
+        raise ValueError("sigma must be finite")
+    radii = tuple(_filter_radius(s, passes) for s in sigma)
+    if max(radii) > MAX_FILTER_RADIUS:
+        raise ValueError(f"sigma gives a box radius outside 0..{MAX_FILTER_RADIUS}")
+    if passes == 1 and (radii[0] > rows or radii[1] > cols):
+        # (the reference indexes before the start of its padded line there)
+        raise ValueError("with passes = 1 the box radius must be in 0..the length of its axis")
+    return sigma, radii
+
+
+class MaskedGaussianFilterTemplate:
+    """Device form of the reference's ``masked_gaussian_filter`` for images of `dtype`
+    (float32 or float64), with `passes` box passes (1..8) per filtered axis."""
+
+    def __init__(self, context: AbstractContext, dtype=np.float32, passes: int = 4) -> None:
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError(f"dtype must be float32 or float64, not {dtype}")
+        _check_passes(passes)
+        self.context = context
+        self.dtype = dtype
+        self.passes = int(passes)
+        self.kernel = context.native_kernel("ksp_masked_filter")
+
+    def instantiate(self, command_queue: AbstractCommandQueue, shape: Sequence[int],
+                    sigma: Sequence[float], batch: Optional[int] = None,
+                    allocator: Optional[accel.AbstractAllocator] = None
+                    ) -> "MaskedGaussianFilter":  # fmt: skip
+        return MaskedGaussianFilter(self, command_queue, shape, sigma, batch, allocator)
+
+
+class MaskedGaussianFilter(accel.Operation):
+    """Concrete :class:`MaskedGaussianFilterTemplate` for images of `shape`, ``(rows,
+    cols)`` or ``(images, rows, cols)``, and a pair `sigma` (axis 0, axis 1).
+
+    .. rubric:: Slots
+
+    **data** : shape, `dtype`
+    **flags** : shape, uint8 (non-zero = flagged, ignored by the filter)
+    **out** : shape, `dtype`; NaN where the filter's support holds no unflagged sample
+
+    The three slots share their dimensions (and so their padding). `out` may be bound to
+    the buffer of `data`: the input is read into the workspace before any result of the
+    same batch of images is written. Images are processed in batches of `batch` (by
+    default as many as fit :data:`DEFAULT_WORKSPACE_BYTES` of workspace, at least one); the
+    workspace is allocated once, here.
+    """
+
+    def __init__(self, template: MaskedGaussianFilterTemplate,
+                 command_queue: AbstractCommandQueue, shape: Sequence[int],
+                 sigma: Sequence[float], batch: Optional[int] = None,
+                 allocator: Optional[accel.AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(command_queue, allocator)
+        shape = tuple(int(s) for s in shape)
+        if len(shape) not in (2, 3):
+            raise ValueError("shape must be (rows, cols) or (images, rows, cols)")
+        images, rows, cols = (1,) + shape if len(shape) == 2 else shape
+        if images < 1:
+            raise ValueError("the number of images must be at least 1")
+        passes = template.passes
+        sigma, radii = _filter_radii(rows, cols, sigma, passes)
+        self.template = template
+        self.shape = shape
+        self.images, self.rows, self.cols = images, rows, cols
+        self.sigma = sigma
+        self.radii = radii
+        self.divisors = tuple(_filter_divisor(r, passes, template.dtype) for r in radii)
+        itemsize = template.dtype.itemsize
+        size = ctypes.c_size_t()
+        _lib.call("ksp_masked_filter_workspace", rows, cols, 1, radii[0], radii[1], passes,
+                  itemsize, ctypes.byref(size))  # fmt: skip
+        if batch is None:
+            batch = max(1, DEFAULT_WORKSPACE_BYTES // size.value)
+        self.batch = max(1, min(int(batch), images))
+        _lib.call("ksp_masked_filter_workspace", rows, cols, self.batch, radii[0], radii[1],
+                  passes, itemsize, ctypes.byref(size))  # fmt: skip
+        self.workspace_bytes = size.value
+        self.workspace = accel.DeviceArray(command_queue.context, (size.value,), np.uint8)
+        dims = tuple(accel.Dimension(s) for s in shape)
+        self.slots["data"] = accel.IOSlot(dims, template.dtype)
+        self.slots["flags"] = accel.IOSlot(dims, np.uint8)
+        self.slots["out"] = accel.IOSlot(dims, template.dtype)
+
+    def _run(self) -> None:
+        data = self.buffer("data")
+        flags = self.buffer("flags")
+        out = self.buffer("out")
+        padded = data.padded_shape
+        if flags.padded_shape != padded or out.padded_shape != padded:
+            raise ValueError("data, flags and out must have the same padding")
+        row_stride = padded[-1]
+        image_stride = padded[-2] * padded[-1]
+        for image0 in range(0, self.images, self.batch):
+            self.command_queue.enqueue_kernel(
+                self.template.kernel,
+                [
+                    data.buffer, flags.buffer, out.buffer, self.rows, self.cols, self.images,
+                    image_stride, row_stride, image0, min(self.batch, self.images - image0),
+                    self.radii[0], self.radii[1], self.template.passes, self.divisors[0],
+                    self.divisors[1], self.template.dtype.itemsize, self.workspace.buffer,
+                    self.workspace_bytes,
+                ],
+            )  # fmt: skip
+
+    def parameters(self) -> Mapping[str, Any]:
+        return {
+            "shape": self.shape, "dtype": self.template.dtype.name,
+            "passes": self.template.passes, "sigma": self.sigma, "radii": self.radii,
+            "batch": self.batch,
+        }  # fmt: skip
+
+
+_filter_context: Optional[AbstractContext] = None
+_filter_default_queue: Any = None
+
+
+def _filter_queue(context: Optional[AbstractContext]) -> Tuple[AbstractContext, Any]:
+    """The context and a queue of it: the caller's context with a queue of its own for this
+    call (nothing of it is kept), or the module's own pair, created on first use and kept."""
+    global _filter_context, _filter_default_queue
+    if context is not None:
+        return context, context.create_command_queue()
+    if _filter_context is None:
+        _filter_context = accel.create_some_context(interactive=False)
+        _filter_default_queue = _filter_context.create_command_queue()
+    return _filter_context, _filter_default_queue
+
+
+def masked_gaussian_filter(data, flags, sigma, out, passes=4, *, context=None):
+    """The reference's ``masked_gaussian_filter``, run on the GPU: fills `out` with the
+    approximate Gaussian filter of the 2-D image `data` (float32 or float64) that ignores
+    the samples whose `flags` (bool or integer, non-zero = flagged) are set; NaN where the
+    filter's support holds no unflagged sample. `sigma` is a pair (axis 0, axis 1) or one
+    value for both. `out` has the dtype and shape of `data` and may be `data` itself;
+    `data` and `flags` are otherwise not modified. Returns ``None``. `context` names the
+    device context to use (no reference to it is kept); by default one context and queue
+    are created on the first call and kept. This is a convenience for arrays on the host:
+    every call builds its operation, allocates the device buffers and workspace and copies
+    both ways. Code that filters many images of one shape keeps a
+    :class:`MaskedGaussianFilter` instead."""
+    data_dtype = getattr(data, "dtype", None)
+    if data_dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError(f"data must be float32 or float64, not {data_dtype}")
+    if not isinstance(out, np.ndarray) or out.dtype != data_dtype:
+        raise TypeError(f"out must be a {data_dtype} array, not {getattr(out, 'dtype', type(out))}")
+    flags = np.asarray(flags)
+    if flags.dtype != np.bool_ and not np.issubdtype(flags.dtype, np.integer):
+        raise TypeError(f"flags must be bool or an integer type, not {flags.dtype}")
+    if data.shape != flags.shape:
+        raise ValueError("shape mismatch between data and flags")
+    if data.shape != out.shape:
+        raise ValueError("shape mismatch between data and out")
+    if data.ndim != 2:
+        raise ValueError("data has wrong number of dimensions")
+    sigma = np.atleast_1d(np.asarray(sigma, np.float64))
+    if sigma.shape == (1,):
+        sigma = np.repeat(sigma, 2)
+    if sigma.shape != (2,):
+        raise ValueError("sigma has wrong number of elements")
+    _check_passes(passes)
+    if data.size == 0:
+        return None  # nothing to fill
+    _filter_radii(data.shape[0], data.shape[1], sigma, passes)
+    context, queue = _filter_queue(context)
+    template = MaskedGaussianFilterTemplate(context, data_dtype, passes)
+    op = template.instantiate(queue, data.shape, sigma)
+    op.ensure_all_bound()
+    op.buffer("data").set(queue, np.ascontiguousarray(data))
+    op.buffer("flags").set(queue, np.ascontiguousarray(flags != 0).view(np.uint8))
+    op()
+    out[...] = op.buffer("out").get(queue)
+    return None
