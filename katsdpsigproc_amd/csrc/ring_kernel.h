@@ -7,12 +7,15 @@
 //     lane) in a RING of 32 step slots; step j = the 64 rows {64 l + j}, i.e. position j of
 //     every lane's run, 64 B each: 4 KiB per slot, 128 KiB for the ring. The ring is
 //     consumed in chunks of 4 steps; the slots of a chunk are refilled with the steps 32
-//     further on (of this strip, then of the next one) one chunk later, so the requests for
+//     further on (of this strip, then of the next one) two chunks after they were read, when
+//     the median has come to that chunk, so the requests for
 //     the next strip are in flight while this one computes and no register holds them;
 //   * a wavefront picks its baseline's sample out of a slot (ds_read_b64), turns it into
 //     numpy's |z| and feeds it straight to the merging median (median_merge.h), which
 //     consumes the run front to back: deviations appear in registers as the samples stream
-//     in. The first H outputs of a lane need the END of the left neighbour's run: they are
+//     in. The reads run two chunks ahead of the median and |z| one chunk, so that the
+//     division's dependent chains issue among the median arithmetic of the chunk before.
+//     The first H outputs of a lane need the END of the left neighbour's run: they are
 //     produced last (band-edge conventions as in MergeMedian::run_src);
 //   * the MAD and the thresholds then run from registers as before (fused_common.h). The few
 //     exact float64 recomputations they ask for (exact_dev) read the visibilities again
@@ -209,18 +212,57 @@ __global__ __launch_bounds__(RING_THREADS) void flagger_ring_kernel(const FusedP
     run_src = start_of(cur);
 #pragma unroll
     for (int j = 0; j < NSLOT; j += 2) issue(j);
-    // Two register sets of raw samples: a chunk is read from the ring while the one before
-    // it is worked on. Chunk 0 of the first strip:
+    // The amplitudes run one chunk ahead of the median and the ring reads two: while the
+    // median works on chunk c, chunk c + 1 is turned into |z| from one register set of raw
+    // samples and chunk c + 2 is read from the ring into the other. |z| (numpy's) of the four
+    // samples of a chunk: the packed short division is computed unconditionally and its
+    // results are pinned in front of the branch -- left to itself the compiler sinks the
+    // division into the else-side of the branch, where its two dependent chains (and the wait
+    // states between packed operations) stand alone in a block; pinned, it is straight-line
+    // code ahead of its use that the scheduler weaves into the median arithmetic of the chunk
+    // before. The branch holds only the general form, which replaces the results in the rare
+    // chunk with a magnitude outside the ordinary range (zero, subnormal, huge, infinite,
+    // NaN) in some lane; `um` watches for NaN and infinity there.
     float2 zz[2][G];
+    auto read_chunk = [&](int chunk, float2 (&z)[G]) {  // (chunk: counted on into the next strip)
+        // (one address per chunk, opaque: or the compiler keeps 16 slot addresses in
+        // registers for good, or adds the slot offset once per read)
+        unsigned ro = rd_off + ((chunk * G) % NSLOT) * RING_SLOT_BYTES;
+        asm volatile("" : "+v"(ro));
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            const unsigned long long w = *(lds_cu64 *)(lds3 + ro + g * RING_SLOT_BYTES);
+            z[g] = make_float2(__uint_as_float((unsigned)w), __uint_as_float((unsigned)(w >> 32)));
+        }
+    };
+    auto convert_chunk = [&](const float2 (&z)[G], float *a, unsigned &um) {
+        static_assert(G == 4, "the pin below names four results");
+        unsigned key = ~0u;
+#pragma unroll
+        for (int g = 0; g < G; g++) key &= ksp_abs_range_key(z[g].x, z[g].y);
+#pragma unroll
+        for (int g = 0; g < G; g += 2)
+            ksp_abs_c64_inrange_x2(z[g].x, z[g].y, z[g + 1].x, z[g + 1].y, a[g], a[g + 1]);
+        asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]));
+        if (ksp_any((key & KSP_ABS_RANGE_BIT) == 0)) {
+#pragma unroll
+            for (int g = 0; g < G; g++) {
+                a[g] = ksp_abs_c64(z[g].x, z[g].y);
+                um = max(um, __float_as_uint(a[g]));
+            }
+        }
+    };
+    // Chunk 0 of a strip is converted at the end of the strip before it (before the loop
+    // for a workgroup's first strip): its amplitudes and its NaN watch are carried into the
+    // strip they belong to.
+    float amp_nxt[G];
+    unsigned umax_nxt = 0;
     {
         constexpr int AH0 = (K - 1) * PER_CHUNK;
         __builtin_amdgcn_s_waitcnt(0x0070 | (AH0 & 15) | ((AH0 >> 4) << 14));
         __syncthreads();
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            const unsigned long long w = *(lds_cu64 *)(lds3 + rd_off + g * RING_SLOT_BYTES);
-            zz[0][g] = make_float2(__uint_as_float((unsigned)w), __uint_as_float((unsigned)(w >> 32)));
-        }
+        read_chunk(0, zz[0]);
+        convert_chunk(zz[0], amp_nxt, umax_nxt);
     }
     const float nanv = __builtin_nanf("");
     const float2 *visf = (const float2 *)p.vis;
@@ -269,21 +311,28 @@ __global__ __launch_bounds__(RING_THREADS) void flagger_ring_kernel(const FusedP
             ring_trace_buf[((blockIdx.x * 8 + wave) * RING_TRACE_STRIPS + trace_it) * RING_TRACE_SLOTS + 4] = __builtin_amdgcn_s_memrealtime();
 #endif
         float amp[STEPS];
-        unsigned umax = 0;
-        // chunk c: make its 4 steps visible, refill the previous chunk's slots, |z|
-        auto load_chunk = [&](auto c_) {
+        unsigned umax = umax_nxt;
+        umax_nxt = 0;
+#pragma unroll
+        for (int g = 0; g < G; g++) amp[g] = amp_nxt[g];
+        // Chunk c, called before the median takes its first sample: refill its slots, read
+        // chunk c + 2, |z| of chunk c + 1. MORE (a type: the strip body is compiled once for
+        // either case, no test of it is left between two barriers): another strip follows.
+        auto load_chunk = [&](auto more_, auto c_) {
+            constexpr bool MORE = decltype(more_)::value;
             constexpr int c = decltype(c_)::value;
-            // Chunk c sits in registers (read during chunk c - 1). Before anything of it is
-            // used: this wavefront's pieces of chunk c + 1 have landed -- it has issued those
-            // of chunks c + 2 .. c + K - 1 after them (the last strip stops at its own last
-            // chunk) -- and its reads of chunk c have returned; behind the barrier that holds
-            // for every wavefront.
-            constexpr int AH = (K - 2) * PER_CHUNK;
+            // The amplitudes of chunk c sit in registers (converted during chunk c - 1), and so
+            // do the raw samples of chunk c + 1 (read during chunk c - 1). Before chunk c + 2 is
+            // read: this wavefront's pieces of it have landed -- it has issued those of chunks
+            // c + 3 .. c + K - 1 after them (the last strip stops at its own last chunk) -- and
+            // its reads of chunk c + 1 have returned, those of chunk c long before; behind the
+            // barrier that holds for every wavefront.
+            constexpr int AH = (K - 3) * PER_CHUNK;
 #ifdef RING_TRACE
             unsigned long long w0;
             asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w0));
 #endif
-            if (more || (c + K - 1) * G + G <= STEPS)
+            if constexpr (MORE || (c + K - 1) * G + G <= STEPS)
                 __builtin_amdgcn_s_waitcnt(0x0070 | (AH & 15) | ((AH >> 4) << 14));
             else
                 __builtin_amdgcn_s_waitcnt(0x0070);
@@ -306,50 +355,27 @@ __global__ __launch_bounds__(RING_THREADS) void flagger_ring_kernel(const FusedP
                 constexpr int j = c * G + 2 * decltype(u_)::value + NSLOT;
                 if constexpr (j < STEPS) {
                     issue(j % NSLOT);
-                } else if (more) {
+                } else if constexpr (MORE) {
                     if constexpr (j == STEPS) run_src = start_nxt;
                     issue(j % NSLOT);
                 }
             });
-            // chunk c + 1 into the other register set (chunk 0 of the next strip at the end)
-            if (c + 1 < NCHUNK || more) {
-                // (one address per chunk, opaque: or the compiler keeps 16 slot addresses in
-                // registers for good, or adds the slot offset once per read)
-                unsigned ro = rd_off + (((c + 1) * G) % NSLOT) * RING_SLOT_BYTES;
-                asm volatile("" : "+v"(ro));
-#pragma unroll
-                for (int g = 0; g < G; g++) {
-                    const unsigned long long w = *(lds_cu64 *)(lds3 + ro + g * RING_SLOT_BYTES);
-                    zz[(c + 1) & 1][g] = make_float2(__uint_as_float((unsigned)w), __uint_as_float((unsigned)(w >> 32)));
-                }
-            }
+            // chunk c + 2 into the register set that chunk c has left. Across the strip
+            // boundary only chunk 0 of the next strip is read, and nothing after the last
+            // strip: raw samples held through the MAD would cost it 8 registers, so chunk 1
+            // is read here, once per strip with nothing to hide the read behind.
+            if constexpr (c == 0) read_chunk(1, zz[1]);
+            if constexpr (c + 2 < NCHUNK || (MORE && c + 2 == NCHUNK)) read_chunk(c + 2, zz[c & 1]);
 #if RING_PRIO == 2
             if ((c + (wave >> 2)) & 1)
                 __builtin_amdgcn_s_setprio(1);
             else
                 __builtin_amdgcn_s_setprio(0);
 #endif
-            const float2 (&z)[G] = zz[c & 1];
-            // |z| (numpy's). The packed short division is computed unconditionally -- straight
-            // line code that the scheduler can weave into the median arithmetic of the samples
-            // before, where a branch around it would leave its dependent chains (and the wait
-            // states between packed operations) on their own -- and replaced by the general form
-            // in the rare chunk that holds a magnitude outside the ordinary range (zero,
-            // subnormal, huge, infinite, NaN) in some lane.
-            unsigned key = ~0u;
-#pragma unroll
-            for (int g = 0; g < G; g++) key &= ksp_abs_range_key(z[g].x, z[g].y);
-#pragma unroll
-            for (int g = 0; g < G; g += 2)
-                ksp_abs_c64_inrange_x2(z[g].x, z[g].y, z[g + 1].x, z[g + 1].y, amp[c * G + g],
-                                       amp[c * G + g + 1]);
-            if (ksp_any((key & KSP_ABS_RANGE_BIT) == 0)) {
-#pragma unroll
-                for (int g = 0; g < G; g++) {
-                    amp[c * G + g] = ksp_abs_c64(z[g].x, z[g].y);
-                    umax = max(umax, __float_as_uint(amp[c * G + g]));
-                }
-            }
+            if constexpr (c + 1 < NCHUNK)
+                convert_chunk(zz[(c + 1) & 1], &amp[(c + 1) * G], umax);
+            else if constexpr (MORE)
+                convert_chunk(zz[(c + 1) & 1], amp_nxt, umax_nxt);
         };
 
         float dev[R];
@@ -371,20 +397,21 @@ __global__ __launch_bounds__(RING_THREADS) void flagger_ring_kernel(const FusedP
                 : "v"(__float_as_uint(x)), "v"(__float_as_uint(m)), "v"(d)
                 : "vcc");
         };
+        // The stream phase of a strip. Only a workgroup's last strip runs the second copy.
+        auto stream = [&](auto more_) __attribute__((always_inline)) {
 #if RING_STOP == 1
-        // diagnostic: ring + |z| only
-        dmax = 0.f;
-        ksp_static_for<NCHUNK>([&](auto c_) {
-            load_chunk(c_);
-            constexpr int c = decltype(c_)::value;
+            // diagnostic: ring + |z| only
+            dmax = 0.f;
+            ksp_static_for<NCHUNK>([&](auto c_) {
+                load_chunk(more_, c_);
+                constexpr int c = decltype(c_)::value;
 #pragma unroll
-            for (int g = 0; g < G; g++) {
-                dev[c * G + g] = amp[c * G + g];
-                dmax += amp[c * G + g];
-            }
-        });
+                for (int g = 0; g < G; g++) {
+                    dev[c * G + g] = amp[c * G + g];
+                    dmax += amp[c * G + g];
+                }
+            });
 #else
-        {
             MergeMedian<R, W> mm;
             mm.pinf = __builtin_inff();
             mm.ninf = -__builtin_inff();
@@ -397,7 +424,7 @@ __global__ __launch_bounds__(RING_THREADS) void flagger_ring_kernel(const FusedP
             auto X = [&](auto i_) -> float {
                 constexpr int i = decltype(i_)::value;
                 if constexpr (i < STEPS) {
-                    if constexpr (i % G == 0) load_chunk(std::integral_constant<int, i / G>{});
+                    if constexpr (i % G == 0) load_chunk(more_, std::integral_constant<int, i / G>{});
                     return amp[i];
                 } else {
                     if constexpr (i == STEPS) {
@@ -521,8 +548,12 @@ __global__ __launch_bounds__(RING_THREADS) void flagger_ring_kernel(const FusedP
                     dev[j] = d;
                 });
             }
-        }
 #endif
+        };
+        if (more)
+            stream(std::true_type{});
+        else
+            stream(std::false_type{});
         RING_STAMP(1);
 #ifdef RING_TRACE
         if (lane_id == 0 && trace_it < RING_TRACE_STRIPS && blockIdx.x < 256) {
