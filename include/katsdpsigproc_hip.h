@@ -345,6 +345,21 @@ int ksp_twodflag(int device, void *stream, const void *data, const uint8_t *in_f
                  int batch, const ksp_twodflag_params *params, void *workspace,
                  size_t workspace_bytes);
 
+/* flag_count (no reference counterpart: the reference's callers count on a host copy).
+ * flags: [rows][stride] uint8. For each of the n_masks (1..8) non-zero masks,
+ * row_counts[m * row_counts_stride + r] = number of columns c with flags[r][c] & masks[m] != 0,
+ * col_counts[m * col_counts_stride + c] = number of rows r with flags[r][c] & masks[m] != 0:
+ * a sample counts at most once per mask, masks may overlap. One launch reads every flag
+ * byte once and produces both. accumulate == 0: both outputs are overwritten (their zero
+ * fill is enqueued on the stream by the launcher); otherwise the counts are added to what
+ * the outputs hold, modulo 2^32. Bytes between cols and stride are never counted, counters
+ * between rows / cols and their stride never written. masks is a HOST pointer. flags or
+ * stride that are not multiples of 16 take a slower, byte-wise path with the same result.
+ * Every argument is checked before any device call. */
+int ksp_flag_count(int device, void *stream, const uint8_t *flags, uint32_t *row_counts,
+                   uint32_t *col_counts, int rows, int cols, int stride, int row_counts_stride,
+                   int col_counts_stride, const uint8_t *masks, int n_masks, int accumulate);
+
 /* ---- masked_gaussian_filter (reference rfi/twodflag.py:254-400) ----
  * Images [images][rows][cols] of float32 (itemsize 4) or float64 (itemsize 8); data, flags
  * (uint8, non-zero = flagged) and out share image_stride and row_stride, in elements

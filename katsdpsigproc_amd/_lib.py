@@ -155,6 +155,10 @@ SIGNATURES = {
         ctypes.c_longlong, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_int,
         c_void_p, c_size_t,
     ],
+    "ksp_flag_count": [
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+        POINTER(ctypes.c_uint8), c_int, c_int,
+    ],
     "ksp_launch_function": [
         c_int, c_void_p, c_void_p, POINTER(ctypes.c_uint), POINTER(ctypes.c_uint), ctypes.c_uint,
         POINTER(c_void_p),

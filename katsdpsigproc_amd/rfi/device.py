@@ -1251,3 +1251,139 @@ class FlaggerHostFromDevice(host.AbstractFlaggerHost):
             fn.buffer("input_flags").set(self.command_queue, input_flags)
         fn()
         return fn.buffer("flags").get(self.command_queue)
+
+
+# ------------------------------------------------------------------------ flag counts
+class FlagCountTemplate:
+    """Count flagged samples per channel and per baseline, on the device (no reference
+    counterpart: the reference's callers count on a host copy of the flags).
+
+    One kernel reads every flag byte once and produces both sets of counts, for up to 8
+    masks at a time; see :class:`host.FlagCountHost` for what is counted.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    masks
+        1 to 8 integers in 1..255: a sample counts for a mask when its flag byte has any
+        of the mask's bits set. Default ``(0xFF,)``: any flag. ``ValueError`` for an empty or
+        too long sequence or a value out of range, ``TypeError`` for a non-integer.
+    transposed
+        ``False`` (default): `flags` is channels x baselines, the flagger's output.
+        ``True``: baselines x channels. The counts are the same either way.
+    accumulate
+        ``False`` (default): every call overwrites both outputs. ``True``: a call adds to
+        what the outputs hold (zero them first); the sums wrap modulo 2**32.
+    tuning
+        The kernel picks its launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.FlagCountHost
+
+    def __init__(self, context: AbstractContext, masks=(0xFF,), transposed: bool = False,
+                 accumulate: bool = False,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        self.context = context
+        self.masks = host.check_flag_masks(masks)
+        self.transposed = bool(transposed)
+        self.accumulate = bool(accumulate)
+        self.tuning = tune.fixed_geometry("FlagCountTemplate", tuning, ())
+        self.kernel = context.native_kernel("ksp_flag_count")
+
+    @classmethod
+    def autotune(cls, context: AbstractContext) -> Mapping[str, Any]:
+        """Nothing to search."""
+        return {}
+
+    def instantiate(self, command_queue: AbstractCommandQueue, channels: int, baselines: int,
+                    allocator: Optional[AbstractAllocator] = None) -> "FlagCount":  # fmt: skip
+        return FlagCount(self, command_queue, channels, baselines, allocator)
+
+
+class FlagCount(accel.Operation):
+    """Concrete :class:`FlagCountTemplate` (``ValueError`` if `channels` or `baselines` is
+    below 1).
+
+    .. rubric:: Slots
+
+    **flags** : channels x baselines (baselines x channels if transposed), uint8
+    **channel_counts** : len(masks) x channels, uint32
+    **baseline_counts** : len(masks) x baselines, uint32
+    """
+
+    def __init__(self, template: FlagCountTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(command_queue, allocator)
+        if channels < 1 or baselines < 1:
+            raise ValueError("channels and baselines must be at least 1")
+        self.template = template
+        self.kernel = template.kernel
+        self.channels = channels
+        self.baselines = baselines
+        self.transposed = template.transposed
+        self.masks = (ctypes.c_uint8 * len(template.masks))(*template.masks)
+        shape = (baselines, channels) if self.transposed else (channels, baselines)
+        n_masks = len(template.masks)
+        self.slots["flags"] = accel.IOSlot((shape[0], accel.Dimension(shape[1])), np.uint8)
+        self.slots["channel_counts"] = accel.IOSlot(
+            (n_masks, accel.Dimension(channels)), np.uint32)  # fmt: skip
+        self.slots["baseline_counts"] = accel.IOSlot(
+            (n_masks, accel.Dimension(baselines)), np.uint32)  # fmt: skip
+
+    def _run(self) -> None:
+        flags = self.buffer("flags")
+        # the kernel counts over rows and columns of `flags` as it lies in memory
+        names = ("baseline_counts", "channel_counts") if self.transposed else (
+            "channel_counts", "baseline_counts")  # fmt: skip
+        row_counts, col_counts = self.buffer(names[0]), self.buffer(names[1])
+        self.command_queue.enqueue_kernel(
+            self.kernel,
+            [
+                flags.buffer,
+                row_counts.buffer,
+                col_counts.buffer,
+                np.int32(flags.shape[0]),
+                np.int32(flags.shape[1]),
+                np.int32(flags.padded_shape[1]),
+                np.int32(row_counts.padded_shape[1]),
+                np.int32(col_counts.padded_shape[1]),
+                self.masks,
+                np.int32(len(self.masks)),
+                np.int32(self.template.accumulate),
+            ],
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        return {
+            "masks": self.template.masks,
+            "transposed": self.transposed,
+            "accumulate": self.template.accumulate,
+            "channels": self.channels,
+            "baselines": self.baselines,
+        }
+
+
+class FlagCountHostFromDevice:
+    """Make a :class:`FlagCountTemplate` callable like :class:`host.FlagCountHost`:
+    channel-major `flags` in, ``(channel_counts, baseline_counts)`` out; allocates on every
+    call. ``ValueError`` for a template that accumulates (a call has nothing to add to)."""
+
+    def __init__(self, template: FlagCountTemplate, command_queue: AbstractCommandQueue) -> None:
+        if template.accumulate:
+            raise ValueError("the template accumulates: there is no single call's result")
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, flags: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        channels, baselines = flags.shape
+        if self.template.transposed:
+            flags = flags.T
+        fn = self.template.instantiate(self.command_queue, channels, baselines)
+        fn.ensure_all_bound()
+        fn.buffer("flags").set(self.command_queue, flags)
+        fn()
+        return (fn.buffer("channel_counts").get(self.command_queue),
+                fn.buffer("baseline_counts").get(self.command_queue))  # fmt: skip

@@ -186,6 +186,49 @@ class ThresholdSumHost(AbstractThresholdHost):
         return flagged.astype(np.uint8) * np.uint8(self.flag_value)
 
 
+def check_flag_masks(masks) -> tuple:
+    """`masks` of a flag counter as a tuple of ints: 1 to 8 values, each 1..255
+    (``ValueError`` otherwise, ``TypeError`` for a value that is not an integer)."""
+    masks = tuple(masks)
+    for mask in masks:
+        if isinstance(mask, (bool, np.bool_)) or not isinstance(mask, (int, np.integer)):
+            raise TypeError(f"mask {mask!r} is not an integer")
+    if not 1 <= len(masks) <= 8:
+        raise ValueError("masks must hold between 1 and 8 values")
+    for mask in masks:
+        if not 1 <= mask <= 255:
+            raise ValueError(f"mask {mask} is outside 1..255")
+    return tuple(int(mask) for mask in masks)
+
+
+class FlagCountHost:
+    """How many samples are flagged, per channel and per baseline.
+
+    For every mask ``m`` of `masks` (1 to 8 integers in 1..255; the default counts any
+    flag), ``channel_counts[m][c]`` is the number of baselines whose flag byte at channel
+    ``c`` has a bit of the mask set, ``baseline_counts[m][b]`` the number of such channels of
+    baseline ``b``. A sample counts at most once per mask; masks may overlap. No reference
+    counterpart.
+    """
+
+    def __init__(self, masks=(0xFF,)) -> None:
+        self.masks = check_flag_masks(masks)
+
+    def __call__(self, flags: np.ndarray):
+        """(channel_counts, baseline_counts), both uint32, ``len(masks)`` rows, for channels x
+        baselines uint8 `flags`."""
+        flags = np.asarray(flags)
+        if flags.ndim != 2 or flags.dtype != np.uint8:
+            raise ValueError("flags must be a 2-D uint8 array")
+        channel_counts = np.empty((len(self.masks), flags.shape[0]), np.uint32)
+        baseline_counts = np.empty((len(self.masks), flags.shape[1]), np.uint32)
+        for i, mask in enumerate(self.masks):
+            hit = (flags & np.uint8(mask)) != 0
+            channel_counts[i] = np.count_nonzero(hit, axis=1)
+            baseline_counts[i] = np.count_nonzero(hit, axis=0)
+        return channel_counts, baseline_counts
+
+
 class FlaggerHost(AbstractFlaggerHost):
     """background -> noise estimate -> threshold (reference rfi/host.py:257-273)."""
 
