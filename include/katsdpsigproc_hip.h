@@ -360,6 +360,44 @@ int ksp_flag_count(int device, void *stream, const uint8_t *flags, uint32_t *row
                    uint32_t *col_counts, int rows, int cols, int stride, int row_counts_stride,
                    int col_counts_stride, const uint8_t *masks, int n_masks, int accumulate);
 
+/* average (no reference counterpart: the reference's callers average in their own code).
+ * Flag-aware averaging over dumps and over groups of channels, bit for bit what
+ * rfi/host.py AveragerHost computes; all arithmetic is float32, one rounding per step.
+ * Every array is [channels][stride] with baselines contiguous and its own row stride, in
+ * elements (vis arrays: complex64 elements). Elements between baselines and a stride are
+ * neither read nor written. Pointers and strides that make every row start a multiple of
+ * 16 bytes take 16-byte loads and stores; anything else a slower element-wise path with
+ * the same result. Every argument is checked before any device call.
+ *
+ * ksp_average_accumulate adds one dump to the accumulators, per sample:
+ *   f = flags | input_flags;  we = f != 0 ? w * 2^-64 : w;
+ *   acc_vis.re += we * vis.re;  acc_vis.im += we * vis.im  (a multiply, then an add);
+ *   acc_weights += we;  acc_flags |= f.
+ * weights may be NULL (w = 1; weights_stride is then ignored). input_flags_mode: 0 none
+ * (input_flags must be NULL), 1 one byte per channel (uint8 [channels]), 2 one byte per
+ * sample ([channels][input_flags_stride]); the stride is ignored unless the mode is 2.
+ * The caller zeroes the accumulators before the first dump.
+ *
+ * ksp_average_finalise writes channels / channel_factor rows of out_vis, out_weights and
+ * out_flags. Per output: re, im, w start at +0 and fl at 0; rows r * channel_factor + k,
+ * k = 0 .. channel_factor - 1, of the accumulators are added (ORed) in that order;
+ * if w < 2^-32 ("every contribution was flagged") re, im and w are multiplied by 2^64;
+ * out_vis = w > 0 ? (re / w, im / w) : (0, 0) with two correctly rounded divisions;
+ * out_weights = w; out_flags = fl if every contribution was flagged, else 0.
+ * clear != 0: the accumulator elements that were read are set to zero in the same pass. */
+int ksp_average_accumulate(int device, void *stream, const void *vis, const uint8_t *flags,
+                           const float *weights, const uint8_t *input_flags,
+                           int input_flags_mode, void *acc_vis, float *acc_weights,
+                           uint8_t *acc_flags, int channels, int baselines, int vis_stride,
+                           int flags_stride, int weights_stride, int input_flags_stride,
+                           int acc_vis_stride, int acc_weights_stride, int acc_flags_stride);
+int ksp_average_finalise(int device, void *stream, void *acc_vis, float *acc_weights,
+                         uint8_t *acc_flags, void *out_vis, float *out_weights,
+                         uint8_t *out_flags, int channels, int baselines, int channel_factor,
+                         int clear, int acc_vis_stride, int acc_weights_stride,
+                         int acc_flags_stride, int out_vis_stride, int out_weights_stride,
+                         int out_flags_stride);
+
 /* ---- masked_gaussian_filter (reference rfi/twodflag.py:254-400) ----
  * Images [images][rows][cols] of float32 (itemsize 4) or float64 (itemsize 8); data, flags
  * (uint8, non-zero = flagged) and out share image_stride and row_stride, in elements

@@ -159,6 +159,14 @@ SIGNATURES = {
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
         POINTER(ctypes.c_uint8), c_int, c_int,
     ],
+    "ksp_average_accumulate": [
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+        c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+    ],
+    "ksp_average_finalise": [
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+        c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+    ],
     "ksp_launch_function": [
         c_int, c_void_p, c_void_p, POINTER(ctypes.c_uint), POINTER(ctypes.c_uint), ctypes.c_uint,
         POINTER(c_void_p),

@@ -14,7 +14,6 @@ inserts transposes where needed.
 """
 
 import ctypes
-import enum
 from abc import ABC, abstractmethod
 from typing import Any, List, Mapping, Optional, Tuple, Type, Union
 
@@ -23,20 +22,9 @@ import numpy as np
 from .. import accel, transpose, tune
 from ..abc import AbstractCommandQueue, AbstractContext
 from ..accel import AbstractAllocator
-from . import host
+from . import BackgroundFlags, host
 
 _THRESHOLD_SUM_DEFAULT_THRESHOLD_FALLOFF = 1.2
-
-
-class BackgroundFlags(enum.Enum):
-    """How input flags are supplied to a backgrounder (reference rfi/device.py:40-46)."""
-
-    NONE = 0
-    CHANNEL = 1
-    FULL = 2
-
-    def __bool__(self) -> bool:
-        return self is not BackgroundFlags.NONE
 
 
 # ----------------------------------------------------------------- abstract interfaces
@@ -1387,3 +1375,283 @@ class FlagCountHostFromDevice:
         fn()
         return (fn.buffer("channel_counts").get(self.command_queue),
                 fn.buffer("baseline_counts").get(self.command_queue))  # fmt: skip
+
+
+# -------------------------------------------------------------------------- averaging
+def _check_average_shape(channels: int, baselines: int, channel_factor: int = 1) -> None:
+    if channels < 1 or baselines < 1:
+        raise ValueError("channels and baselines must be at least 1")
+    if channel_factor < 1 or channels % channel_factor:
+        raise ValueError("channel_factor must be at least 1 and divide channels")
+
+
+class AccumulateTemplate:
+    """Add one dump of visibilities to device-resident accumulators, leaving flagged
+    samples out (no reference counterpart: the reference's callers average in their own
+    code). :class:`host.AveragerHost` defines the arithmetic of ``add``; the kernel matches
+    it bit for bit. :class:`FinaliseTemplate` turns the accumulators into averages.
+
+    The accumulators are read, updated and written back by every call: zero them once
+    before the first dump (``buffer("acc_vis").zero(queue)`` and likewise for
+    ``acc_weights`` and ``acc_flags``); :class:`Finalise` zeroes them again if built with
+    ``clear=True``.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    use_weights
+        ``True`` (default): there is a `weights` slot. ``False``: every weight is 1.
+    input_flags
+        :class:`BackgroundFlags`: whether there is an `input_flags` slot that is ORed into
+        the flags, one byte per channel (CHANNEL) or per sample (FULL)
+    tuning
+        The kernel picks its launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.AveragerHost
+
+    def __init__(self, context: AbstractContext, use_weights: bool = True,
+                 input_flags: BackgroundFlags = BackgroundFlags.NONE,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        self.context = context
+        self.use_weights = bool(use_weights)
+        self.input_flags = BackgroundFlags(input_flags)
+        self.tuning = tune.fixed_geometry("AccumulateTemplate", tuning, ())
+        self.kernel = context.native_kernel("ksp_average_accumulate")
+
+    @classmethod
+    def autotune(cls, context: AbstractContext) -> Mapping[str, Any]:
+        """Nothing to search."""
+        return {}
+
+    def instantiate(self, command_queue: AbstractCommandQueue, channels: int, baselines: int,
+                    allocator: Optional[AbstractAllocator] = None) -> "Accumulate":  # fmt: skip
+        return Accumulate(self, command_queue, channels, baselines, allocator)
+
+
+class Accumulate(accel.Operation):
+    """Concrete :class:`AccumulateTemplate` (``ValueError`` if `channels` or `baselines` is
+    below 1).
+
+    .. rubric:: Slots
+
+    **vis** : channels x baselines, complex64
+    **flags** : channels x baselines, uint8 (any non-zero byte means flagged)
+    **weights** : channels x baselines, float32 (only with ``use_weights``)
+    **input_flags** : channels or channels x baselines, uint8 (only if the mode is not NONE)
+    **acc_vis** : channels x baselines, complex64
+    **acc_weights** : channels x baselines, float32
+    **acc_flags** : channels x baselines, uint8
+
+    Every two-dimensional slot has a dimension object of its own for the baselines, so
+    `vis` and `flags` can be compounded with the flagger's slots of those names and take
+    their padding.
+    """
+
+    def __init__(self, template: AccumulateTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(command_queue, allocator)
+        _check_average_shape(channels, baselines)
+        self.template = template
+        self.kernel = template.kernel
+        self.channels = channels
+        self.baselines = baselines
+
+        def full(dtype) -> accel.IOSlot:
+            return accel.IOSlot((channels, accel.Dimension(baselines)), dtype)
+
+        self.slots["vis"] = full(np.complex64)
+        self.slots["flags"] = full(np.uint8)
+        if template.use_weights:
+            self.slots["weights"] = full(np.float32)
+        if template.input_flags == BackgroundFlags.FULL:
+            self.slots["input_flags"] = full(np.uint8)
+        elif template.input_flags == BackgroundFlags.CHANNEL:
+            self.slots["input_flags"] = accel.IOSlot((channels,), np.uint8)
+        self.slots["acc_vis"] = full(np.complex64)
+        self.slots["acc_weights"] = full(np.float32)
+        self.slots["acc_flags"] = full(np.uint8)
+
+    def _run(self) -> None:
+        mode = self.template.input_flags
+        vis, flags = self.buffer("vis"), self.buffer("flags")
+        weights = self.buffer("weights") if self.template.use_weights else None
+        in_flags = self.buffer("input_flags") if mode else None
+        acc = [self.buffer(name) for name in ("acc_vis", "acc_weights", "acc_flags")]
+        self.command_queue.enqueue_kernel(
+            self.kernel,
+            [
+                vis.buffer,
+                flags.buffer,
+                weights.buffer if weights is not None else None,
+                in_flags.buffer if in_flags is not None else None,
+                np.int32(mode.value),
+                acc[0].buffer,
+                acc[1].buffer,
+                acc[2].buffer,
+                np.int32(self.channels),
+                np.int32(self.baselines),
+                np.int32(vis.padded_shape[1]),
+                np.int32(flags.padded_shape[1]),
+                np.int32(weights.padded_shape[1] if weights is not None else 0),
+                np.int32(in_flags.padded_shape[1] if mode == BackgroundFlags.FULL else 0),
+                np.int32(acc[0].padded_shape[1]),
+                np.int32(acc[1].padded_shape[1]),
+                np.int32(acc[2].padded_shape[1]),
+            ],
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        return {
+            "use_weights": self.template.use_weights,
+            "input_flags": self.template.input_flags.name,
+            "channels": self.channels,
+            "baselines": self.baselines,
+        }
+
+
+class FinaliseTemplate:
+    """Turn the accumulators of :class:`Accumulate` into averages: sum every
+    `channel_factor` adjacent channels in order, divide by the summed weight, and report the
+    flags of outputs whose contributions were all flagged (:meth:`host.AveragerHost.finalise`,
+    matched bit for bit).
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    channel_factor
+        Number of adjacent channels per output channel, at least 1 (``ValueError``); it
+        must divide the channels given to :meth:`instantiate` (``ValueError`` there)
+    clear
+        ``True`` (default): the kernel zeroes the accumulators it has read, in the same
+        pass, ready for the next dump. ``False``: they are left as they are.
+    tuning
+        Nothing to tune, any key is a ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.AveragerHost
+
+    def __init__(self, context: AbstractContext, channel_factor: int = 1, clear: bool = True,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        if channel_factor < 1:
+            raise ValueError("channel_factor must be at least 1")
+        self.context = context
+        self.channel_factor = int(channel_factor)
+        self.clear = bool(clear)
+        self.tuning = tune.fixed_geometry("FinaliseTemplate", tuning, ())
+        self.kernel = context.native_kernel("ksp_average_finalise")
+
+    @classmethod
+    def autotune(cls, context: AbstractContext) -> Mapping[str, Any]:
+        """Nothing to search."""
+        return {}
+
+    def instantiate(self, command_queue: AbstractCommandQueue, channels: int, baselines: int,
+                    allocator: Optional[AbstractAllocator] = None) -> "Finalise":  # fmt: skip
+        return Finalise(self, command_queue, channels, baselines, allocator)
+
+
+class Finalise(accel.Operation):
+    """Concrete :class:`FinaliseTemplate` (``ValueError`` if `channels` or `baselines` is
+    below 1 or the template's `channel_factor` does not divide `channels`).
+
+    .. rubric:: Slots
+
+    **acc_vis** : channels x baselines, complex64
+    **acc_weights** : channels x baselines, float32
+    **acc_flags** : channels x baselines, uint8
+    **vis** : channels // channel_factor x baselines, complex64
+    **weights** : channels // channel_factor x baselines, float32
+    **flags** : channels // channel_factor x baselines, uint8
+    """
+
+    def __init__(self, template: FinaliseTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(command_queue, allocator)
+        _check_average_shape(channels, baselines, template.channel_factor)
+        self.template = template
+        self.kernel = template.kernel
+        self.channels = channels
+        self.baselines = baselines
+        out_channels = channels // template.channel_factor
+        for prefix, rows in (("acc_", channels), ("", out_channels)):
+            for name, dtype in (("vis", np.complex64), ("weights", np.float32), ("flags", np.uint8)):
+                self.slots[prefix + name] = accel.IOSlot(
+                    (rows, accel.Dimension(baselines)), dtype)  # fmt: skip
+
+    def _run(self) -> None:
+        names = ("acc_vis", "acc_weights", "acc_flags", "vis", "weights", "flags")
+        buffers = [self.buffer(name) for name in names]
+        self.command_queue.enqueue_kernel(
+            self.kernel,
+            [b.buffer for b in buffers]
+            + [
+                np.int32(self.channels),
+                np.int32(self.baselines),
+                np.int32(self.template.channel_factor),
+                np.int32(self.template.clear),
+            ]
+            + [np.int32(b.padded_shape[1]) for b in buffers],
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        return {
+            "channel_factor": self.template.channel_factor,
+            "clear": self.template.clear,
+            "channels": self.channels,
+            "baselines": self.baselines,
+        }
+
+
+class AveragerHostFromDevice:
+    """Present an :class:`AccumulateTemplate` and a :class:`FinaliseTemplate` through the
+    ``add`` / ``finalise`` interface of :class:`host.AveragerHost`. The operations are
+    instantiated and the shared accumulators allocated and zeroed once, here; with a
+    `finalise_template` built with ``clear=False`` the accumulators keep their sums across
+    :meth:`finalise`, unlike the host class."""
+
+    def __init__(self, accumulate_template: AccumulateTemplate,
+                 finalise_template: FinaliseTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int) -> None:  # fmt: skip
+        self.command_queue = command_queue
+        self.input_flags = accumulate_template.input_flags
+        self.use_weights = accumulate_template.use_weights
+        self._accumulate = accumulate_template.instantiate(command_queue, channels, baselines)
+        self._finalise = finalise_template.instantiate(command_queue, channels, baselines)
+        shared = ("acc_vis", "acc_weights", "acc_flags")
+        self._sequence = accel.OperationSequence(
+            command_queue, [("accumulate", self._accumulate), ("finalise", self._finalise)],
+            compounds={name: ["accumulate:" + name, "finalise:" + name] for name in shared})
+        self._sequence.ensure_all_bound()
+        for name in shared:
+            self._sequence.buffer(name).zero(command_queue)
+
+    def add(self, vis: np.ndarray, flags: np.ndarray, weights: Optional[np.ndarray] = None,
+            input_flags: Optional[np.ndarray] = None) -> None:  # fmt: skip
+        if input_flags is not None and not self.input_flags:
+            raise TypeError("input_flags were provided but not included in the template")
+        if input_flags is None and self.input_flags:
+            raise TypeError("input_flags were expected but not provided")
+        if weights is not None and not self.use_weights:
+            raise TypeError("weights were provided but not included in the template")
+        fn = self._accumulate
+        fn.buffer("vis").set(self.command_queue, vis)
+        fn.buffer("flags").set(self.command_queue, flags)
+        if self.use_weights:
+            if weights is None:
+                weights = np.ones(fn.buffer("weights").shape, np.float32)
+            fn.buffer("weights").set(self.command_queue, weights)
+        if input_flags is not None:
+            fn.buffer("input_flags").set(self.command_queue, input_flags)
+        fn()
+
+    def finalise(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        fn = self._finalise
+        fn()
+        return tuple(fn.buffer(name).get(self.command_queue)
+                     for name in ("vis", "weights", "flags"))  # fmt: skip

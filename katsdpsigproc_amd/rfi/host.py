@@ -17,7 +17,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import MAD_NORMAL
+from . import MAD_NORMAL, BackgroundFlags
 
 
 class AbstractBackgroundHost(ABC):
@@ -227,6 +227,134 @@ class FlagCountHost:
             channel_counts[i] = np.count_nonzero(hit, axis=1)
             baseline_counts[i] = np.count_nonzero(hit, axis=0)
         return channel_counts, baseline_counts
+
+
+class AveragerHost:
+    """Flag-aware averaging of visibilities over dumps and over groups of channels.
+
+    :meth:`add` accumulates one dump into ``acc_vis`` (complex64), ``acc_weights`` (float32)
+    and ``acc_flags`` (uint8), all channels x baselines; :meth:`finalise` sums every
+    `channel_factor` adjacent channels, divides by the weight, returns
+    ``(vis, weights, flags)`` of ``channels // channel_factor`` rows and clears the state.
+    No reference counterpart; this class is the definition that the device operations
+    (:class:`.device.AccumulateTemplate`, :class:`.device.FinaliseTemplate`) match bit for
+    bit.
+
+    A flagged sample is not dropped but enters with its weight scaled by 2**-64. An output
+    with at least one unflagged contribution is then, to rounding, the weighted average of
+    the unflagged ones; an output whose contributions were all flagged carries the average
+    of the flagged data (its sums are scaled back by 2**64) and the OR of their flags.
+    One set of accumulators serves both cases.
+
+    Every step is one float32 operation, rounded once, in the order written in the methods
+    (a multiply and then an add, never a fused multiply-add; two real divisions, not a
+    complex one). NaN, infinity and denormals go through as IEEE arithmetic gives them.
+
+    The caller's side of the contract: a weight is 0 ("no data") or within about
+    [2**-30, 2**30], and an output sums at most about 2**30 contributions, so that the
+    threshold 2**-32 on the summed weight tells "some unflagged data" from "flagged data
+    only". An output with no data at all has weight 0, visibility 0 and flags 0.
+
+    Parameters
+    ----------
+    channels, baselines
+        Shape of a dump (``ValueError`` if below 1)
+    channel_factor
+        Number of adjacent channels per output channel (``ValueError`` unless it is at
+        least 1 and divides `channels`)
+    input_flags
+        :class:`BackgroundFlags` (or its value): whether :meth:`add` also takes a static
+        mask, per channel (CHANNEL) or per sample (FULL), that is ORed into the flags
+    """
+
+    FLAGGED_SCALE = np.float32(2.0 ** -64)
+    UNSCALE = np.float32(2.0 ** 64)
+    ALL_FLAGGED_BELOW = np.float32(2.0 ** -32)
+
+    def __init__(self, channels: int, baselines: int, channel_factor: int = 1,
+                 input_flags=BackgroundFlags.NONE) -> None:  # fmt: skip
+        if channels < 1 or baselines < 1:
+            raise ValueError("channels and baselines must be at least 1")
+        if channel_factor < 1 or channels % channel_factor:
+            raise ValueError("channel_factor must be at least 1 and divide channels")
+        self.channels = channels
+        self.baselines = baselines
+        self.channel_factor = channel_factor
+        self.input_flags = BackgroundFlags(input_flags)
+        self.acc_vis = np.zeros((channels, baselines), np.complex64)
+        self.acc_weights = np.zeros((channels, baselines), np.float32)
+        self.acc_flags = np.zeros((channels, baselines), np.uint8)
+
+    def add(self, vis: np.ndarray, flags: np.ndarray, weights: Optional[np.ndarray] = None,
+            input_flags: Optional[np.ndarray] = None) -> None:  # fmt: skip
+        """Accumulate one dump: complex64 `vis`, uint8 `flags` (non-zero = flagged) and
+        float32 `weights` (``None``: 1 everywhere), all channels x baselines, and uint8
+        `input_flags` of shape (channels,) or (channels, baselines) as the mode says
+        (``TypeError`` if given with mode NONE or missing otherwise)."""
+        if input_flags is not None and not self.input_flags:
+            raise TypeError("input_flags were provided but the mode is NONE")
+        if input_flags is None and self.input_flags:
+            raise TypeError("input_flags were expected but not provided")
+        shape = (self.channels, self.baselines)
+        vis = np.asarray(vis, np.complex64)
+        f = np.asarray(flags, np.uint8)
+        if vis.shape != shape or f.shape != shape:
+            raise ValueError("vis and flags must be channels x baselines")
+        if input_flags is not None:
+            mask = np.asarray(input_flags, np.uint8)
+            if self.input_flags == BackgroundFlags.CHANNEL:
+                if mask.shape != (self.channels,):
+                    raise ValueError("input_flags must have one byte per channel")
+                mask = mask[:, np.newaxis]
+            elif mask.shape != shape:
+                raise ValueError("input_flags must be channels x baselines")
+            f = f | mask
+        if weights is None:
+            w = np.ones(shape, np.float32)
+        else:
+            w = np.asarray(weights, np.float32)
+            if w.shape != shape:
+                raise ValueError("weights must be channels x baselines")
+        bad = f != 0
+        with np.errstate(all="ignore"):
+            we = np.where(bad, w * self.FLAGGED_SCALE, w)
+            self.acc_vis.real[...] = self.acc_vis.real + we * vis.real
+            self.acc_vis.imag[...] = self.acc_vis.imag + we * vis.imag
+            self.acc_weights[...] = self.acc_weights + we
+        self.acc_flags |= f  # (f is zero wherever the sample is not flagged)
+
+    def finalise(self):
+        """``(vis, weights, flags)`` of ``channels // channel_factor`` x baselines from what
+        has been accumulated; the state is zero again afterwards."""
+        rows = self.channels // self.channel_factor
+        grouped = (rows, self.channel_factor, self.baselines)
+        acc_re = self.acc_vis.real.reshape(grouped)
+        acc_im = self.acc_vis.imag.reshape(grouped)
+        acc_w = self.acc_weights.reshape(grouped)
+        acc_fl = self.acc_flags.reshape(grouped)
+        re = np.zeros((rows, self.baselines), np.float32)
+        im = np.zeros((rows, self.baselines), np.float32)
+        w = np.zeros((rows, self.baselines), np.float32)
+        fl = np.zeros((rows, self.baselines), np.uint8)
+        with np.errstate(all="ignore"):
+            for k in range(self.channel_factor):
+                re = re + acc_re[:, k]
+                im = im + acc_im[:, k]
+                w = w + acc_w[:, k]
+                fl = fl | acc_fl[:, k]
+            allbad = w < self.ALL_FLAGGED_BELOW
+            w = np.where(allbad, w * self.UNSCALE, w)
+            re = np.where(allbad, re * self.UNSCALE, re)
+            im = np.where(allbad, im * self.UNSCALE, im)
+            some = w > 0
+            vis = np.zeros((rows, self.baselines), np.complex64)
+            vis.real[...] = np.where(some, re / w, np.float32(0))
+            vis.imag[...] = np.where(some, im / w, np.float32(0))
+        out_flags = np.where(allbad, fl, np.uint8(0))
+        self.acc_vis[...] = 0
+        self.acc_weights[...] = 0
+        self.acc_flags[...] = 0
+        return vis, w, out_flags
 
 
 class FlaggerHost(AbstractFlaggerHost):
