@@ -98,6 +98,20 @@ int ksp_memset_async(int device, void *ptr, int value, size_t bytes, void *strea
 
 /* ========================================================================== *
  *  Kernels. One launcher per reference kernel.
+ *
+ *  Sub-views. For every launcher, an array argument that comes with a row stride may
+ *  be a sub-view of a larger array: a column block of a wider array, a buffer with a
+ *  padding of its own, a pointer some elements into an allocation (one-dimensional
+ *  arguments such as noise, mask or per-channel flags may start anywhere as well).
+ *  With `cols` the extent of a row (baselines or channels, whichever is contiguous):
+ *    - nothing outside [row * stride, row * stride + cols) of any row is written,
+ *      zero fills included, and no input is written at all;
+ *    - results do not depend on what lies outside those ranges;
+ *    - alignment of pointers and strides affects speed only (16-byte loads and stores
+ *      where every row allows them, element-wise access otherwise, same result),
+ *      except where a launcher states a requirement: ksp_flagger_fused states one
+ *      for `vis`.
+ *  (ksp_twodflag, ksp_masked_filter and the FFT wrappers describe layouts of their own.)
  * ========================================================================== */
 
 /* transpose (reference: transpose.mako:44-73; launch transpose.py:146-167).
@@ -183,7 +197,11 @@ int ksp_threshold_sum_cm(int device, void *stream, const float *deviations, cons
  * to n_windows doubles (falloff^-k, rfi/host.py:215). workspace: NULL, or 64 bytes of
  * device memory owned by the caller, zeroed once when allocated and used by one
  * launch at a time (scheduling counters: with it the last strips of a large array are
- * handed to whichever XCD is free; the kernel leaves it zeroed again). */
+ * handed to whichever XCD is free; the kernel leaves it zeroed again).
+ * Alignment: vis must be 16-byte aligned and vis_stride even (both are checked before any
+ * device call); every other array may be any sub-view. Only the `baselines` bytes of each
+ * row of flags are cleared and written: one linear fill when flags_stride == baselines,
+ * a row-wise fill kernel otherwise. */
 int ksp_flagger_fused(int device, void *stream, const void *vis, const uint8_t *in_flags,
                       uint8_t *flags, float *deviations, float *noise, int channels,
                       int baselines, int vis_stride, int in_flags_stride, int flags_stride,

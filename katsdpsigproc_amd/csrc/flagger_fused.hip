@@ -22,8 +22,8 @@
 //     is recomputed exactly in float64 from the LDS amplitudes, because the host path
 //     is float64 after the amplitude (reference rfi/host.py:148-163, 235-245) and the
 //     flags must match it bit for bit.
-//   * flags are zero-filled by a memset node ahead of the kernel; the kernel only
-//     writes the (sparse) non-zero bytes.
+//   * flags are zero-filled ahead of the kernel (a memset node, or a fill kernel when the
+//     rows are not contiguous); the kernel only writes the (sparse) non-zero bytes.
 //
 // Roofline: HBM, 9 algorithmic bytes per sample (8 read + 1 written).
 #include "flagger_fused_kernel.h"
@@ -66,6 +66,41 @@ static int ksp_fused_launch_other_width(int width, int device, hipStream_t s,
     if (width <= 21) return ksp_fused_launch_w19_21(width, device, s, p, ev0, ev1);
     if (width <= 27) return ksp_fused_launch_w23_27(width, device, s, p, ev0, ev1);
     return ksp_fused_launch_w29_31(width, device, s, p, ev0, ev1);
+}
+
+// Zero fill of `cols` bytes in each of `rows` rows that lie `stride` bytes apart. The rows are
+// cut into the 16-byte aligned pieces of memory they touch, one piece per lane: a piece that
+// lies wholly inside its row is one 16-byte store, the ragged first and last piece of a row are
+// written byte by byte, and nothing between the rows is touched. `pieces` = pieces per row,
+// enough for any alignment of a row's start: (cols + 15) / 16 + 1.
+__global__ __launch_bounds__(256) void fused_zero_rows_kernel(uint8_t *__restrict__ base, int rows,
+                                                              int cols, size_t stride, int pieces)
+{
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t row = gid / (unsigned)pieces;
+    if (row >= (size_t)rows) return;
+    const int k = (int)(gid - row * (unsigned)pieces);
+    const uintptr_t begin = (uintptr_t)base + row * stride, end = begin + (uintptr_t)cols;
+    const uintptr_t piece = (begin & ~(uintptr_t)15) + 16 * (uintptr_t)k;
+    if (piece >= end) return;
+    if (piece >= begin && piece + 16 <= end) {
+        *(uint4 *)piece = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+        const uintptr_t lo = piece > begin ? piece : begin;
+        const uintptr_t hi = piece + 16 < end ? piece + 16 : end;
+        for (uintptr_t a = lo; a < hi; a++) *(uint8_t *)a = 0;
+    }
+}
+
+hipError_t fused_zero_flags(const FusedParams &p, hipStream_t s)
+{
+    if (p.flags_stride == p.baselines)
+        return hipMemsetAsync(p.flags, 0, (size_t)p.channels * p.baselines, s);
+    const int pieces = (p.baselines + 15) / 16 + 1;
+    const size_t lanes = (size_t)p.channels * pieces;
+    hipLaunchKernelGGL(fused_zero_rows_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s,
+                       p.flags, p.channels, p.baselines, (size_t)p.flags_stride, pieces);
+    return hipGetLastError();
 }
 
 extern "C" int ksp_flagger_fused_profile(void *start_event, void *stop_event)
@@ -196,7 +231,7 @@ extern "C" int ksp_flagger_fused(int device, void *stream, const void *vis,
         // first strip's loads, a completion counter before the first flag byte -- was built
         // and measured: step time unchanged, 0.376 against 0.377 ms clean and 0.518 against
         // 0.519 with interference; the memset stays.)
-        KSP_CHECK(hipMemsetAsync(p.flags, 0, (size_t)(p.channels - 1) * p.flags_stride + p.baselines, s));
+        KSP_CHECK(fused_zero_flags(p, s));
         const int whole = baselines - baselines % 8;
         if (whole < baselines) {
             FusedParams t = p;

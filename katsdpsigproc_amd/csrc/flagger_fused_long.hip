@@ -112,7 +112,7 @@ static int launch_long(int device, hipStream_t s, const FusedParams &p, hipEvent
 {
     const int runs = (p.channels + 63) >> 6;
     const size_t lds_bytes = sizeof(float) * S * (runs * LONG_RUN + 8) + sizeof(double) * 256 * S;
-    KSP_CHECK(hipMemsetAsync(p.flags, 0, (size_t)(p.channels - 1) * p.flags_stride + p.baselines, s));
+    KSP_CHECK(fused_zero_flags(p, s));
     auto kern = flagger_long_kernel<NR, S, WIDTH>;
     // opt in once per device to the whole 160 KiB (the size in use depends on the channel count)
     static std::atomic<bool> attr_set[64];

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests import inputs
+from tests.subviews import SENTINEL, flat_device_array, read_flat, sentinel_array
 
 pytestmark = pytest.mark.gpu
 
@@ -21,7 +22,6 @@ BASELINES = [1, 3, 4, 5, 15, 16, 17, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025
              WORKGROUP_COLS - 1, WORKGROUP_COLS, WORKGROUP_COLS + 1]  # fmt: skip
 CHANNELS = [1, 2, 7, 8]
 N_DUMPS = 4
-SENTINEL = 0xAB
 
 
 @pytest.fixture(scope="module")
@@ -120,10 +120,6 @@ def assert_same(want, got, what=""):
     assert not bad.any(), (
         f"{what}: {np.count_nonzero(bad)} of {bad.size} differ, first at "
         f"{np.argwhere(bad)[0]}: want {want[bad][0]!r}, got {got[bad][0]!r}")  # fmt: skip
-
-
-def sentinel_array(padded_shape, dtype):
-    return np.full(padded_shape, SENTINEL, np.uint8).repeat(np.dtype(dtype).itemsize, -1).view(dtype)
 
 
 def write_padded(queue, array, data):
@@ -289,29 +285,6 @@ def test_clear(baselines, context, command_queue):
             assert not acc.view(np.uint8).any(), f"{name} was not cleared"
 
 
-def flat_device_array(context, queue, dtype, data, stride, offset):
-    """A 1-D device array full of sentinels with `data` at rows of `stride` elements, starting
-    `offset` elements in; returns (array, pointer to the first element of data)."""
-    from katsdpsigproc_amd import accel
-
-    rows, cols = data.shape
-    host_array = sentinel_array((offset + rows * stride + 16,), dtype)
-    host_array[offset : offset + rows * stride].reshape(rows, stride)[:, :cols] = data
-    array = accel.DeviceArray(context, host_array.shape, dtype)
-    array.set(queue, host_array)
-    return array, ctypes.c_void_p(array.buffer.ptr + offset * np.dtype(dtype).itemsize)
-
-
-def read_flat(queue, array, shape, stride, offset):
-    """The data rows of a flat_device_array, after checking every other byte of it."""
-    rows, cols = shape
-    raw = array.get(queue)
-    inside = np.zeros(raw.shape, bool)
-    inside[offset : offset + rows * stride].reshape(rows, stride)[:, :cols] = True
-    assert np.all(raw[~inside].view(np.uint8) == SENTINEL), "wrote outside the rows"
-    return np.ascontiguousarray(raw[offset : offset + rows * stride].reshape(rows, stride)[:, :cols])
-
-
 @pytest.mark.parametrize("offset", [1, 4, 12])
 @pytest.mark.parametrize("mode", ["NONE", "CHANNEL", "FULL"])
 def test_raw_abi_unaligned(mode, offset, context, command_queue):
@@ -334,13 +307,13 @@ def test_raw_abi_unaligned(mode, offset, context, command_queue):
     device_index = context.device.index
     stream = ctypes.c_void_p(queue.stream)
     for vis, flags, weights, mask in dumps:
-        d_vis = flat_device_array(context, queue, np.complex64, vis, strides["vis"], offset)
-        d_flags = flat_device_array(context, queue, np.uint8, flags, strides["flags"], offset)
-        d_weights = flat_device_array(context, queue, np.float32, weights, strides["weights"], offset)
+        d_vis = flat_device_array(context, queue, np.complex64, vis, strides["vis"], offset, poison=True)
+        d_flags = flat_device_array(context, queue, np.uint8, flags, strides["flags"], offset, poison=True)
+        d_weights = flat_device_array(context, queue, np.float32, weights, strides["weights"], offset, poison=True)
         if mode == "CHANNEL":
-            d_mask = flat_device_array(context, queue, np.uint8, mask[np.newaxis, :], channels, offset)
+            d_mask = flat_device_array(context, queue, np.uint8, mask[np.newaxis, :], channels, offset, poison=True)
         elif mode == "FULL":
-            d_mask = flat_device_array(context, queue, np.uint8, mask, strides["mask"], offset)
+            d_mask = flat_device_array(context, queue, np.uint8, mask, strides["mask"], offset, poison=True)
         else:
             d_mask = (None, None)
         _lib.call("ksp_average_accumulate", device_index, stream, d_vis[1], d_flags[1],

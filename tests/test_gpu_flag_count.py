@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests import inputs
+from tests import inputs, subviews
 
 pytestmark = pytest.mark.gpu
 
@@ -122,25 +122,20 @@ def test_padding(rows, cols, context, command_queue):
 def call_abi(context, queue, flags, stride, offset, masks=(0xFF,)):
     """ksp_flag_count on `flags` laid out with `stride` bytes per row, starting `offset`
     bytes into an allocation; the outputs have stride rows + 3 / cols + 5."""
-    from katsdpsigproc_amd import _lib, accel
+    from katsdpsigproc_amd import _lib
 
     rows, cols = flags.shape
-    host_in = np.full(offset + rows * stride + 16, 0xFF, np.uint8)
-    view = host_in[offset : offset + rows * stride].reshape(rows, stride)
-    view[:, :cols] = flags
-    dev_in = accel.DeviceArray(context, host_in.shape, np.uint8)
-    dev_in.set(queue, host_in)
-    row_out = accel.DeviceArray(context, (len(masks), rows + 3), np.uint32)
-    col_out = accel.DeviceArray(context, (len(masks), cols + 5), np.uint32)
-    for out in (row_out, col_out):
-        out.set(queue, np.full(out.shape, 0xABABABAB, np.uint32))
+    dev_in = subviews.DeviceView(context, queue, np.uint8, flags, stride, offset, poison=True)
+    blank = subviews.sentinel_array  # (counts start as sentinels: the launcher overwrites them)
+    row_out = subviews.DeviceView(context, queue, np.uint32, blank((len(masks), rows), np.uint32),
+                                  rows + 3)  # fmt: skip
+    col_out = subviews.DeviceView(context, queue, np.uint32, blank((len(masks), cols), np.uint32),
+                                  cols + 5)  # fmt: skip
     _lib.call("ksp_flag_count", context.device.index, ctypes.c_void_p(queue.stream),
-              ctypes.c_void_p(dev_in.buffer.ptr + offset), ctypes.c_void_p(row_out.buffer.ptr),
-              ctypes.c_void_p(col_out.buffer.ptr), rows, cols, stride, rows + 3, cols + 5,
+              dev_in.ptr, row_out.ptr, col_out.ptr, rows, cols, stride, rows + 3, cols + 5,
               (ctypes.c_uint8 * len(masks))(*masks), len(masks), 0)  # fmt: skip
-    row_counts, col_counts = row_out.get(queue), col_out.get(queue)
-    assert np.all(row_counts[:, rows:] == 0xABABABAB) and np.all(col_counts[:, cols:] == 0xABABABAB)
-    return row_counts[:, :rows], col_counts[:, :cols]
+    dev_in.read("flags")
+    return row_out.read("row_counts"), col_out.read("col_counts")
 
 
 @pytest.mark.parametrize("offset", [0, 1])
