@@ -224,12 +224,15 @@ int ksp_flagger_fused_supported(int channels, int width, int n_windows);
 
 /* Which kernels the calling thread's LAST ksp_flagger_fused call launched (no reference
  * counterpart: the tests use it to prove which path they exercised): 0 none, or a sum of
- * 1 = flagger_fused_kernel (strips of 4 baselines, up to 4096 channels),
- * 2 = flagger_long_kernel (4097-12288 channels),
- * 4 = flagger_ring_kernel (persistent, strips of 8 baselines, 4096 channels, complex input
+ * STRIP = flagger_fused_kernel (strips of 4 baselines, up to 4096 channels),
+ * LONG = flagger_long_kernel (4097-12288 channels),
+ * RING = flagger_ring_kernel (persistent, strips of 8 baselines, 4096 channels, complex input
  *     without input flags, no deviations output, at most 4 windows; chosen from about 4
- *     strips per compute unit on, see ksp_flagger_fused_ring_mode); 5 = ring kernel plus the
- *     4-baseline kernel for a remainder of fewer than 8 baselines. */
+ *     strips per compute unit on, see ksp_flagger_fused_ring_mode); RING | STRIP = ring kernel
+ *     plus the 4-baseline kernel for a remainder of fewer than 8 baselines. */
+#define KSP_FUSED_PATH_STRIP 1
+#define KSP_FUSED_PATH_LONG 2
+#define KSP_FUSED_PATH_RING 4
 int ksp_flagger_fused_last_path(void);
 
 /* Which launches of the calling thread take the persistent ring kernel where it applies

@@ -6,6 +6,7 @@ This is the only place where Python meets native code. The shared library
 the library is missing or a call fails, a :class:`RuntimeError` is raised.
 """
 
+import contextlib
 import ctypes
 import os
 import sys
@@ -15,6 +16,11 @@ from ctypes import c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_native", "libkatsdpsigproc_hip.so")
 ABI_VERSION = 5
+
+# ksp_flagger_fused_last_path: which kernels the last fused launch took (KSP_FUSED_PATH_*)
+FUSED_PATH_STRIP = 1
+FUSED_PATH_LONG = 2
+FUSED_PATH_RING = 4
 
 _lib = None
 
@@ -243,7 +249,18 @@ def call(name: str, *args) -> int:
     return rc
 
 
+@contextlib.contextmanager
+def fused_ring_mode(mode: int):
+    """ksp_flagger_fused_ring_mode set to `mode` (1: the ring kernel wherever it applies, 0: by
+    size, -1: never) for the calling thread inside the block, the previous mode after it."""
+    previous = call("ksp_flagger_fused_ring_mode", mode)
+    try:
+        yield
+    finally:
+        call("ksp_flagger_fused_ring_mode", previous)
+
+
 __all__ = [
-    "ABI_VERSION", "DeviceProps", "TwodflagOffsets", "TwodflagParams", "LIB_PATH", "SIGNATURES", "byref", "call", "declared_symbols",
-    "last_error", "load",
+    "ABI_VERSION", "FUSED_PATH_LONG", "FUSED_PATH_RING", "FUSED_PATH_STRIP", "DeviceProps", "TwodflagOffsets", "TwodflagParams", "LIB_PATH", "SIGNATURES", "byref", "call", "declared_symbols",
+    "fused_ring_mode", "last_error", "load",
 ]  # fmt: skip

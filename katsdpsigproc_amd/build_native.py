@@ -76,9 +76,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     for src in sources:
         obj = os.path.join(OUT_DIR, os.path.basename(src)[:-4] + ".o")
         objects.append(obj)
-        # (every source is a dependency of every object: one translation unit includes
-        # another's .hip file)
-        if force or _stale(obj, sources + headers):
+        if force or _stale(obj, [src] + headers):
             own = PER_SOURCE_FLAGS.get(os.path.basename(src), [])
             jobs.append([hipcc] + FLAGS + own + extra + ["-c", src, "-o", obj])
 

@@ -33,41 +33,6 @@ static thread_local hipEvent_t g_prof_start = nullptr, g_prof_stop = nullptr;
 // Kernels launched by this thread's last ksp_flagger_fused call (ksp_flagger_fused_last_path).
 static thread_local int g_last_path = 0;
 
-// widths other than 13 (flagger_fused_w*.hip): lanes always own 64 channels there
-int ksp_fused_launch_w3_7(int width, int device, hipStream_t s, const FusedParams &p,
-                          hipEvent_t ev0, hipEvent_t ev1);
-int ksp_fused_launch_w9_11(int width, int device, hipStream_t s, const FusedParams &p,
-                           hipEvent_t ev0, hipEvent_t ev1);
-int ksp_fused_launch_w15_17(int width, int device, hipStream_t s, const FusedParams &p,
-                            hipEvent_t ev0, hipEvent_t ev1);
-int ksp_fused_launch_w19_21(int width, int device, hipStream_t s, const FusedParams &p,
-                            hipEvent_t ev0, hipEvent_t ev1);
-int ksp_fused_launch_w23_27(int width, int device, hipStream_t s, const FusedParams &p,
-                            hipEvent_t ev0, hipEvent_t ev1);
-int ksp_fused_launch_w29_31(int width, int device, hipStream_t s, const FusedParams &p,
-                            hipEvent_t ev0, hipEvent_t ev1);
-
-// more than 4096 channels (flagger_fused_long.hip)
-int ksp_fused_long_supported(int channels, int width);
-int ksp_fused_launch_long(int device, hipStream_t s, const FusedParams &p, hipEvent_t ev0,
-                          hipEvent_t ev1);
-
-// 4096 channels, whole strips of 8 baselines (flagger_ring.hip)
-bool ksp_ring_supported(const FusedParams &p, int width);
-int ksp_ring_launch(int width, int device, hipStream_t s, const FusedParams &p, int n_cu,
-                    hipEvent_t ev0, hipEvent_t ev1);
-
-static int ksp_fused_launch_other_width(int width, int device, hipStream_t s,
-                                        const FusedParams &p, hipEvent_t ev0, hipEvent_t ev1)
-{
-    if (width <= 7) return ksp_fused_launch_w3_7(width, device, s, p, ev0, ev1);
-    if (width <= 11) return ksp_fused_launch_w9_11(width, device, s, p, ev0, ev1);
-    if (width <= 17) return ksp_fused_launch_w15_17(width, device, s, p, ev0, ev1);
-    if (width <= 21) return ksp_fused_launch_w19_21(width, device, s, p, ev0, ev1);
-    if (width <= 27) return ksp_fused_launch_w23_27(width, device, s, p, ev0, ev1);
-    return ksp_fused_launch_w29_31(width, device, s, p, ev0, ev1);
-}
-
 // Zero fill of `cols` bytes in each of `rows` rows that lie `stride` bytes apart. The rows are
 // cut into the 16-byte aligned pieces of memory they touch, one piece per lane: a piece that
 // lies wholly inside its row is one 16-byte store, the ragged first and last piece of a row are
@@ -137,18 +102,13 @@ extern "C" int ksp_flagger_fused_supported(int channels, int width, int n_window
     return channels >= 1 && width >= 3 && width <= 31 && (width & 1);
 }
 
-extern "C" int ksp_flagger_fused(int device, void *stream, const void *vis,
-                                 const uint8_t *in_flags, uint8_t *flags, float *deviations,
-                                 float *noise, int channels, int baselines, int vis_stride,
-                                 int in_flags_stride, int flags_stride, int dev_stride, int width,
-                                 int is_amplitude, int flags_mode, int threshold_kind,
-                                 double n_sigma, const double *scales64, int n_windows,
-                                 int flag_value, void *workspace)
+// The argument checks of ksp_flagger_fused; n_windows is normalised for the simple threshold.
+static int check_fused_args(const void *vis, const uint8_t *in_flags, const uint8_t *flags,
+                            const float *deviations, int channels, int baselines, int vis_stride,
+                            int in_flags_stride, int flags_stride, int dev_stride, int width,
+                            int flags_mode, int threshold_kind, const double *scales64,
+                            int &n_windows)
 {
-    // profiling events are consumed by this call whatever its outcome
-    const hipEvent_t ev0 = g_prof_start, ev1 = g_prof_stop;
-    g_prof_start = g_prof_stop = nullptr;
-    g_last_path = 0;
     KSP_REQUIRE(vis != nullptr && flags != nullptr, "NULL buffer");
     KSP_REQUIRE(channels >= 1 && baselines >= 0, "bad shape");
     KSP_REQUIRE(vis_stride >= baselines && flags_stride >= baselines, "stride smaller than row");
@@ -168,10 +128,28 @@ extern "C" int ksp_flagger_fused(int device, void *stream, const void *vis,
     // 16-byte loads of baseline pairs need even strides and an aligned base
     KSP_REQUIRE((vis_stride & 1) == 0, "vis_stride must be even");
     KSP_REQUIRE(((uintptr_t)vis & 15) == 0, "vis must be 16-byte aligned");
-    if (baselines == 0) return 0;
-    KSP_CHECK(hipSetDevice(device));
+    return 0;
+}
 
-    FusedParams p;
+// The strip schedule of a launch over p.baselines baselines (fused_common.h, FusedParams):
+// with a workspace for the counters, the last 1/16 of a large launch's strips are dynamic.
+static void set_schedule(FusedParams &p, bool have_workspace)
+{
+    p.n_strips = ksp_divup(p.baselines, FUSED_STRIP);
+    p.n_dyn = 0;
+    if (have_workspace && p.n_strips >= 2048) p.n_dyn = (p.n_strips >> FUSED_DYN_SHIFT) & ~63;
+    p.n_static = p.n_strips - p.n_dyn;
+    p.dyn_blocks = p.n_dyn * FUSED_DYN_OVER / 4;
+}
+
+static FusedParams make_params(const void *vis, const uint8_t *in_flags, uint8_t *flags,
+                               float *deviations, float *noise, int channels, int baselines,
+                               int vis_stride, int in_flags_stride, int flags_stride,
+                               int dev_stride, int is_amplitude, int flags_mode,
+                               int threshold_kind, double n_sigma, const double *scales64,
+                               int n_windows, int flag_value, void *workspace, int n_cu)
+{
+    FusedParams p = {};
     p.vis = vis;
     p.in_flags = in_flags;
     p.flags = flags;
@@ -188,73 +166,125 @@ extern "C" int ksp_flagger_fused(int device, void *stream, const void *vis,
     p.threshold_kind = threshold_kind;
     p.n_windows = n_windows;
     p.flag_value = flag_value;
-    p.n_strips = ksp_divup(baselines, FUSED_STRIP);
     p.work = (unsigned *)workspace;
-    int n_cu = 0;
-    p.n_dyn = 0;
-    if (workspace != nullptr && p.n_strips >= 2048) p.n_dyn = (p.n_strips >> FUSED_DYN_SHIFT) & ~63;
-    p.n_static = p.n_strips - p.n_dyn;
-    p.dyn_blocks = p.n_dyn * FUSED_DYN_OVER / 4;
-    {
-        static std::atomic<int> cus[64];
-        int n = (device >= 0 && device < 64) ? cus[device].load(std::memory_order_relaxed) : 0;
-        if (n == 0) {
-            KSP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device));
-            if (device >= 0 && device < 64) cus[device].store(n, std::memory_order_relaxed);
-        }
-        p.first_round = 2 * n;
-        n_cu = n;
-    }
+    set_schedule(p, workspace != nullptr);
+    p.first_round = 2 * n_cu;
 #ifdef KSP_DIAG
-    p.trace = nullptr;
-    {
-        const char *dbg = getenv("KSP_FUSED_DEBUG_STOP");
-        p.debug_stop = dbg ? atoi(dbg) : 0;
-    }
+    const char *dbg = getenv("KSP_FUSED_DEBUG_STOP");
+    p.debug_stop = dbg ? atoi(dbg) : 0;
 #endif
     p.n_sigma = n_sigma;
     for (int k = 0; k < KSP_MAX_WINDOWS; k++)
         p.scales[k] = (scales64 != nullptr && k < n_windows) ? scales64[k] : 0.0;
+    return p;
+}
 
-    hipStream_t s = (hipStream_t)stream;
-    // The persistent ring kernel takes the whole strips of 8 baselines of a 4096-channel
-    // launch without input flags; a ragged remainder (< 8 baselines) goes to the
-    // 4-baseline kernel.
-    // It pays from about 4 strips per workgroup on (measured, tools/time_ring_sizes.py: 0.089 ms
-    // against 0.065 at 4096 baselines, 0.133 = 0.132 at 8192, 0.218 against 0.236 at 16384,
-    // 0.384 against 0.431 at 32768); ksp_flagger_fused_ring_mode (tests, diagnostics; initial
-    // value from KSP_FUSED_RING=1 / 0 in the environment) forces the choice.
-    const int mode = ring_mode();
-    const bool want_ring = mode != 0 ? mode > 0 : baselines / 8 >= 4 * n_cu;
+// Baselines [first, first + count) of a launch that the ring kernel accepts (complex
+// visibilities, no input flags, no deviations), as a launch of its own on a static schedule.
+static FusedParams columns(const FusedParams &p, int first, int count)
+{
+    FusedParams t = p;
+    t.vis = (const float2 *)p.vis + first;
+    t.flags = p.flags + first;
+    if (p.noise != nullptr) t.noise = p.noise + first;
+    t.baselines = count;
+    set_schedule(t, false);
+    return t;
+}
+
+// Which kernels take a launch: KSP_FUSED_PATH_* bits, the strip kernel's channels per lane (4,
+// 16 or 64), and the baselines beyond the ring kernel's last whole strip of 8.
+struct FusedPath {
+    int bits, lanes, tail;
+};
+
+// `mode` is ksp_flagger_fused_ring_mode's (tests, diagnostics; initial value from
+// KSP_FUSED_RING=1 / 0 in the environment): it forces the choice otherwise made by size.
+// The persistent ring kernel takes the whole strips of 8 baselines of a 4096-channel
+// launch without input flags; a ragged remainder (< 8 baselines) goes to the
+// 4-baseline kernel.
+// It pays from about 4 strips per workgroup on (measured, tools/time_ring_sizes.py: 0.089 ms
+// against 0.065 at 4096 baselines, 0.133 = 0.132 at 8192, 0.218 against 0.236 at 16384,
+// 0.384 against 0.431 at 32768).
+static FusedPath choose_path(const FusedParams &p, int width, int n_cu, int mode)
+{
+    const bool want_ring = mode != 0 ? mode > 0 : p.baselines / 8 >= 4 * n_cu;
     if (want_ring && width == 13 && ksp_ring_supported(p, width)) {
+        const int tail = p.baselines % 8;
+        return {KSP_FUSED_PATH_RING | (tail != 0 ? KSP_FUSED_PATH_STRIP : 0), 64, tail};
+    }
+    if (p.channels > 4096) return {KSP_FUSED_PATH_LONG, 64, 0};
+    // widths other than 13 and more than 4 SumThreshold windows: lanes always own 64 channels
+    const bool wide = p.threshold_kind == KSP_THRESHOLD_SUM && p.n_windows > 4;
+    if (width != 13 || wide || p.channels > 64 * 16) return {KSP_FUSED_PATH_STRIP, 64, 0};
+    return {KSP_FUSED_PATH_STRIP, p.channels <= 64 * 4 ? 4 : 16, 0};
+}
+
+// The strip kernel for up to 4096 channels: width 13 is compiled here, the other widths in
+// the flagger_fused_w*.hip files.
+static int launch_strip(int lanes, int width, int device, hipStream_t s, const FusedParams &p,
+                        hipEvent_t ev0, hipEvent_t ev1)
+{
+#define KSP_WIDTH(W) case W: return ksp_fused_launch_width<W>(device, s, p, ev0, ev1)
+    switch (width) {
+    case 13:
+        if (lanes == 64) return launch_fused<64, 13>(device, s, p, ev0, ev1);
+        if (lanes == 4) return launch_fused<4, 13>(device, s, p, ev0, ev1);
+        return launch_fused<16, 13>(device, s, p, ev0, ev1);
+    KSP_WIDTH(3); KSP_WIDTH(5); KSP_WIDTH(7); KSP_WIDTH(9); KSP_WIDTH(11);
+    KSP_WIDTH(15); KSP_WIDTH(17); KSP_WIDTH(19); KSP_WIDTH(21); KSP_WIDTH(23);
+    KSP_WIDTH(25); KSP_WIDTH(27); KSP_WIDTH(29); KSP_WIDTH(31);
+    }
+#undef KSP_WIDTH
+    ksp_set_error("fused flagger: width %d is not compiled here", width);
+    return (int)hipErrorInvalidValue;
+}
+
+extern "C" int ksp_flagger_fused(int device, void *stream, const void *vis,
+                                 const uint8_t *in_flags, uint8_t *flags, float *deviations,
+                                 float *noise, int channels, int baselines, int vis_stride,
+                                 int in_flags_stride, int flags_stride, int dev_stride, int width,
+                                 int is_amplitude, int flags_mode, int threshold_kind,
+                                 double n_sigma, const double *scales64, int n_windows,
+                                 int flag_value, void *workspace)
+{
+    // profiling events are consumed by this call whatever its outcome
+    const hipEvent_t ev0 = g_prof_start, ev1 = g_prof_stop;
+    g_prof_start = g_prof_stop = nullptr;
+    g_last_path = 0;
+    int rc = check_fused_args(vis, in_flags, flags, deviations, channels, baselines, vis_stride,
+                              in_flags_stride, flags_stride, dev_stride, width, flags_mode,
+                              threshold_kind, scales64, n_windows);
+    if (rc != 0 || baselines == 0) return rc;
+    KSP_CHECK(hipSetDevice(device));
+    static KspPerDevice<int> cus;
+    int n_cu = cus.get(device);
+    if (n_cu == 0) {
+        KSP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+        cus.set(device, n_cu);
+    }
+    const FusedParams p = make_params(vis, in_flags, flags, deviations, noise, channels, baselines,
+                                      vis_stride, in_flags_stride, flags_stride, dev_stride,
+                                      is_amplitude, flags_mode, threshold_kind, n_sigma, scales64,
+                                      n_windows, flag_value, workspace, n_cu);
+    hipStream_t s = (hipStream_t)stream;
+    const FusedPath path = choose_path(p, width, n_cu, ring_mode());
+    if (path.bits & KSP_FUSED_PATH_RING) {
         // (Letting the ring kernel zero-fill `flags` itself -- write-through stores beside the
         // first strip's loads, a completion counter before the first flag byte -- was built
         // and measured: step time unchanged, 0.376 against 0.377 ms clean and 0.518 against
         // 0.519 with interference; the memset stays.)
         KSP_CHECK(fused_zero_flags(p, s));
-        const int whole = baselines - baselines % 8;
-        if (whole < baselines) {
-            FusedParams t = p;
-            t.vis = (const float2 *)p.vis + whole;
-            t.flags = p.flags + whole;
-            if (p.noise != nullptr) t.noise = p.noise + whole;
-            t.baselines = baselines - whole;
-            t.n_strips = ksp_divup(t.baselines, FUSED_STRIP);
-            t.n_dyn = 0;
-            t.n_static = t.n_strips;
-            t.dyn_blocks = 0;
-            const int rc = launch_fused<64, 13>(device, s, t, nullptr, nullptr, false);
+        if (path.tail != 0) {
+            const FusedParams t = columns(p, baselines - path.tail, path.tail);
+            rc = launch_fused<64, 13>(device, s, t, nullptr, nullptr, false);
             if (rc != 0) return rc;
-            g_last_path |= 1;
+            g_last_path |= KSP_FUSED_PATH_STRIP;
         }
-        g_last_path |= 4;
+        g_last_path |= KSP_FUSED_PATH_RING;
         return ksp_ring_launch(width, device, s, p, n_cu, ev0, ev1);
     }
-    g_last_path = channels > 4096 ? 2 : 1;
-    if (channels > 4096) return ksp_fused_launch_long(device, s, p, ev0, ev1);
-    if (width != 13) return ksp_fused_launch_other_width(width, device, s, p, ev0, ev1);
-    const bool wide = threshold_kind == KSP_THRESHOLD_SUM && n_windows > 4;  // (lanes of 64 channels)
-    if (channels <= 64 * 4 && !wide) return launch_fused<4, 13>(device, s, p, ev0, ev1);
-    if (channels <= 64 * 16 && !wide) return launch_fused<16, 13>(device, s, p, ev0, ev1);
-    return launch_fused<64, 13>(device, s, p, ev0, ev1);
+    g_last_path = path.bits;
+    if (path.bits == KSP_FUSED_PATH_LONG) return ksp_fused_launch_long(device, s, p, ev0, ev1);
+    return launch_strip(path.lanes, width, device, s, p, ev0, ev1);
 }

@@ -4,11 +4,8 @@
 // the other odd widths 3..31 for R = 64 -- one translation unit per few widths so that
 // they compile in parallel.
 #pragma once
-#include <hip/hip_ext.h>
-
-#include <atomic>
-
-#include "fused_common.h"
+#include "fused_dispatch.h"
+#include "launch.h"
 
 #ifndef FUSED_DYN_SHIFT
 #define FUSED_DYN_SHIFT 4  // the last 1 / 2^n of the strips are scheduled dynamically
@@ -183,22 +180,15 @@ inline int launch_fused(int device, hipStream_t s, const FusedParams &p, hipEven
     // all flags start at zero; the kernels only write the (rare) non-zero ones
     if (zero_fill) KSP_CHECK(fused_zero_flags(p, s));
     auto kern = flagger_fused_kernel<R, WIDTH>;
-    // the opt-in to more than 64 KiB of dynamic LDS is per device (one context per
-    // device in one process is a supported arrangement, reference doc/user/init.rst:4-6)
-    static std::atomic<bool> attr_set[64];
-    if (device < 0 || device >= 64 || !attr_set[device].load(std::memory_order_acquire)) {
-        KSP_CHECK(hipFuncSetAttribute((const void *)kern,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        if (device >= 0 && device < 64) attr_set[device].store(true, std::memory_order_release);
+    bool first = false;
+    const int rc = ksp_lds_opt_in<flagger_fused_kernel<R, WIDTH>>(device, lds_bytes, &first);
+    if (rc != 0) return rc;
 #ifdef KSP_DIAG
-        if (getenv("KSP_FUSED_DEBUG_OCC")) {
-            int nb = -1;
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, FUSED_THREADS, lds_bytes);
-            fprintf(stderr, "flagger_fused_kernel<%d>: %d workgroups/CU, LDS %zu B\n", R, nb, lds_bytes);
-        }
-#endif
+    if (first && getenv("KSP_FUSED_DEBUG_OCC")) {
+        int nb = -1;
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)kern, FUSED_THREADS, lds_bytes);
+        fprintf(stderr, "flagger_fused_kernel<%d>: %d workgroups/CU, LDS %zu B\n", R, nb, lds_bytes);
     }
-#ifdef KSP_DIAG
     const char *trace_path = getenv("KSP_FUSED_DEBUG_TRACE");
     if (trace_path != nullptr) {
         // diagnostic run: collect per-wavefront phase time stamps and dump them
@@ -221,15 +211,6 @@ inline int launch_fused(int device, hipStream_t s, const FusedParams &p, hipEven
         return 0;
     }
 #endif
-    // events armed by ksp_flagger_fused_profile time exactly this kernel (not the
-    // zero-fill before it)
-    if (ev0 != nullptr)
-        hipExtLaunchKernelGGL(kern, dim3(p.n_static + p.dyn_blocks), dim3(FUSED_THREADS),
-                              lds_bytes, s, ev0, ev1, 0, p);
-    else
-        hipLaunchKernelGGL(kern, dim3(p.n_static + p.dyn_blocks), dim3(FUSED_THREADS), lds_bytes,
-                           s, p);
-    KSP_LAUNCH_CHECK();
-    return 0;
+    return ksp_launch_timed(kern, dim3(p.n_static + p.dyn_blocks), dim3(FUSED_THREADS), lds_bytes, s,
+                            ev0, ev1, p);
 }
-

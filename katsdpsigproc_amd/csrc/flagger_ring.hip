@@ -1,9 +1,5 @@
 // Persistent ring kernel for the fused flagger at 4096 channels (ring_kernel.h): the
 // instantiations and the entry points flagger_fused.hip dispatches to.
-#include <hip/hip_ext.h>
-
-#include <atomic>
-
 #include "ring_kernel.h"
 
 bool ksp_ring_supported(const FusedParams &p, int width) { return ring_supported(p, width); }

@@ -57,13 +57,6 @@ struct FusedParams {
     double scales[KSP_MAX_WINDOWS];
 };
 
-// All flags start at zero; the kernels only write the (rare) non-zero ones. Only the
-// `baselines` bytes of each row are cleared: `flags` may be a column block of a wider array,
-// whose bytes between the rows belong to someone else. Contiguous rows (every launch whose
-// width is a multiple of the 128-byte row alignment, the benchmark's among them) take one
-// linear fill, anything else a fill kernel (flagger_fused.hip).
-hipError_t fused_zero_flags(const FusedParams &p, hipStream_t s);
-
 // LDS image of one strip: 8 rows (one per baseline) of float32 amplitudes. Lane l of
 // the owning wavefront works on channels [l*R, (l+1)*R); its run is padded by 4 words
 // so that 16-byte reads of consecutive lanes fall in consecutive 16-byte slots, and

@@ -16,9 +16,8 @@
 // Numerics (reference rfi/host.py:157-163 on float32 input): numpy.median stays in
 // float32 -- even count -> float32(a + b) * 0.5 -- and the 1.4826 scale is applied
 // in float64; the float32 output is that float64 product rounded once.
-#include <atomic>
-
 #include "bitplane.h"
+#include "launch.h"
 #include "rank.h"
 
 #define KSP_MAD_NORMAL 1.4826
@@ -352,13 +351,9 @@ extern "C" int ksp_madnz_t(int device, void *stream, const float *in, float *noi
         // long rows (madnz_long.h): in LDS up to MADL_STAGE_MAX channels, else streamed
         const int vec = (stride % 4 == 0) && ((uintptr_t)in % 16 == 0);
         if (channels <= MADL_STAGE_MAX) {
-            static std::atomic<bool> attr_set[64];
-            if (device < 0 || device >= 64 || !attr_set[device].load(std::memory_order_acquire)) {
-                KSP_CHECK(hipFuncSetAttribute((const void *)madnz_t_long_kernel<true>,
-                                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              (int)(sizeof(unsigned) * MADL_STAGE_MAX)));
-                if (device >= 0 && device < 64) attr_set[device].store(true, std::memory_order_release);
-            }
+            const int rc = ksp_lds_opt_in<madnz_t_long_kernel<true>>(
+                device, sizeof(unsigned) * MADL_STAGE_MAX);
+            if (rc != 0) return rc;
             const size_t lds = sizeof(unsigned) * 4 * (size_t)ksp_divup(channels, 4);
             hipLaunchKernelGGL(madnz_t_long_kernel<true>, dim3(baselines), dim3(MADL_THREADS), lds,
                                s, in, noise, channels, stride, vec);
@@ -417,12 +412,8 @@ extern "C" int ksp_madnz(int device, void *stream, const float *in, float *noise
     KSP_CHECK(hipSetDevice(device));
     if (channels <= 4096) {
         const size_t lds = sizeof(float) * MADNZ_STRIP * MADNZ_ROW;
-        static std::atomic<bool> attr_set[64];
-        if (device < 0 || device >= 64 || !attr_set[device].load(std::memory_order_acquire)) {
-            KSP_CHECK(hipFuncSetAttribute((const void *)madnz_strip_kernel,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (device >= 0 && device < 64) attr_set[device].store(true, std::memory_order_release);
-        }
+        const int rc = ksp_lds_opt_in<madnz_strip_kernel>(device, lds);
+        if (rc != 0) return rc;
         hipLaunchKernelGGL(madnz_strip_kernel, dim3(ksp_divup(baselines, MADNZ_STRIP)),
                            dim3(64 * MADNZ_STRIP), lds, (hipStream_t)stream, in, noise, channels,
                            baselines, stride);

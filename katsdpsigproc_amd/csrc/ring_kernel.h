@@ -33,7 +33,8 @@
 // `vis_pad`) takes care of that: 2.8 TB/s for the DMA pattern alone at stride 256 KiB,
 // 5.1-5.4 with 8..48 elements of padding.
 #pragma once
-#include "fused_common.h"
+#include "fused_dispatch.h"
+#include "launch.h"
 
 #ifndef RING_STOP
 #define RING_STOP 0  // diagnostic builds: 1 = ring and |z| only, 2 = + median, 3 = + MAD
@@ -676,12 +677,8 @@ inline int launch_ring(int device, hipStream_t s, const FusedParams &p_in, int n
     FusedParams p = p_in;
     p.n_strips = p.baselines / RING_STRIP;  // whole strips only (the caller does the rest)
     auto kern = flagger_ring_kernel<WIDTH>;
-    static std::atomic<bool> attr_set[64];
-    if (device < 0 || device >= 64 || !attr_set[device].load(std::memory_order_acquire)) {
-        KSP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)RingLayout::LDS_BYTES));
-        if (device >= 0 && device < 64) attr_set[device].store(true, std::memory_order_release);
-    }
+    int rc = ksp_lds_opt_in<flagger_ring_kernel<WIDTH>>(device, RingLayout::LDS_BYTES);
+    if (rc != 0) return rc;
     const int grid = p.n_strips < n_cu ? p.n_strips : n_cu;
     // static part of the schedule: all but the last two strips of a workgroup's even share,
     // as far as every list's tickets below n_static * grid / 8 are strips of the array
@@ -705,12 +702,8 @@ inline int launch_ring(int device, hipStream_t s, const FusedParams &p_in, int n
         KSP_CHECK(hipMemsetAsync(tb, 0, sizeof(ring_trace_buf), s));
     }
 #endif
-    if (ev0 != nullptr)
-        hipExtLaunchKernelGGL(kern, dim3(grid), dim3(RING_THREADS), RingLayout::LDS_BYTES, s, ev0, ev1,
-                              0, p);
-    else
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(RING_THREADS), RingLayout::LDS_BYTES, s, p);
-    KSP_LAUNCH_CHECK();
+    rc = ksp_launch_timed(kern, dim3(grid), dim3(RING_THREADS), RingLayout::LDS_BYTES, s, ev0, ev1, p);
+    if (rc != 0) return rc;
 #ifdef RING_TRACE
     if (const char *path = getenv("KSP_RING_TRACE")) {
         KSP_CHECK(hipStreamSynchronize(s));

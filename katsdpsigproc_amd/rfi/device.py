@@ -799,14 +799,10 @@ class ThresholdSumDevice(AbstractThresholdDevice):
 
 
 def ctypes_float_array(values):
-    import ctypes
-
     return (ctypes.c_float * len(values))(*[float(v) for v in values])
 
 
 def ctypes_double_array(values):
-    import ctypes
-
     return (ctypes.c_double * len(values))(*[float(v) for v in values])
 
 

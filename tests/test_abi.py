@@ -80,3 +80,32 @@ def test_argument_validation_without_gpu(lib):
                                ctypes.c_void_p(8), 16, 4, 16, 11.0,
                                (ctypes.c_float * 9)(), 9, 1, 0)  # fmt: skip
     assert rc != 0 and "n_windows" in _lib.last_error()
+
+
+def test_fused_ring_mode_and_path_names(lib):
+    """_lib.fused_ring_mode sets the calling thread's mode for its block and restores the one
+    before, in order when nested and when the block raises; the path names are the header's."""
+    from katsdpsigproc_amd import _lib
+
+    def mode():
+        return lib.ksp_flagger_fused_ring_mode(7)  # (7: query only)
+
+    start = mode()
+    with _lib.fused_ring_mode(1):
+        assert mode() == 1
+        with _lib.fused_ring_mode(-1):
+            assert mode() == -1
+            with _lib.fused_ring_mode(0):
+                assert mode() == 0
+            assert mode() == -1
+        assert mode() == 1
+        with pytest.raises(ZeroDivisionError):
+            with _lib.fused_ring_mode(-1):
+                assert mode() == -1
+                1 / 0
+        assert mode() == 1
+    assert mode() == start
+    defines = dict(re.findall(r"^#define (KSP_FUSED_PATH_\w+) (\d+)$", open(HEADER).read(), re.M))
+    names = ("FUSED_PATH_STRIP", "FUSED_PATH_LONG", "FUSED_PATH_RING")
+    assert defines == {"KSP_" + name: str(getattr(_lib, name)) for name in names}
+    assert [getattr(_lib, name) for name in names] == [1, 2, 4]

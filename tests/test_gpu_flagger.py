@@ -1,7 +1,6 @@
 """GPU parity tests of the flagger: the reference-shaped kernel sequence, the fused
 single-pass kernel (bit-identical to FlaggerHost), and the raw C-ABI entry point."""
 
-import contextlib
 import ctypes
 import hashlib
 
@@ -85,20 +84,6 @@ def run_fused(template, command_queue, vis, in_flags=None, **threshold_args):
     return out
 
 
-@contextlib.contextmanager
-def force_ring():
-    """Launches of fewer than about 8192 baselines are left to the 4-baseline kernel unless
-    told otherwise (ksp_flagger_fused_ring_mode): the tests of the ring kernel on small arrays
-    say so."""
-    from katsdpsigproc_amd import _lib
-
-    previous = _lib.call("ksp_flagger_fused_ring_mode", 1)
-    try:
-        yield
-    finally:
-        _lib.call("ksp_flagger_fused_ring_mode", previous)
-
-
 def check_ring_path(template, command_queue, vis, in_flags, threshold_args, out):
     """Launches that keep the deviations take the 4-baseline kernel; without them a
     4096-channel launch of complex visibilities without input flags (width 13, at least 8
@@ -120,11 +105,11 @@ def check_ring_path(template, command_queue, vis, in_flags, threshold_args, out)
     fn.buffer("vis").set(command_queue, vis)
     for _ in range(2):  # (twice: the scheduling counters must be left as they were found)
         fn.buffer("flags").set(command_queue, np.full(vis.shape, 255, np.uint8))
-        with force_ring():
+        with _lib.fused_ring_mode(1):
             fn()
         path = _lib.call("ksp_flagger_fused_last_path")
-        assert path & 4, f"expected the ring kernel, last path = {path}"
-        assert (path & 1) == (1 if vis.shape[1] % 8 else 0)
+        assert path & _lib.FUSED_PATH_RING, f"expected the ring kernel, last path = {path}"
+        assert bool(path & _lib.FUSED_PATH_STRIP) == bool(vis.shape[1] % 8)
         np.testing.assert_array_equal(fn.buffer("flags").get(command_queue), out["flags"])
         np.testing.assert_array_equal(fn.buffer("noise").get(command_queue), out["noise"])
 
@@ -389,10 +374,11 @@ class TestFused:
         fn.ensure_all_bound()
         assert not fn.slots["deviations"].is_bound()
         fn.buffer("vis").set(command_queue, vis)
-        with force_ring():
+        with _lib.fused_ring_mode(1):
             fn()
         if channels == 4096:
-            assert _lib.call("ksp_flagger_fused_last_path") & 4  # nothing optional: the ring kernel
+            # nothing optional: the ring kernel
+            assert _lib.call("ksp_flagger_fused_last_path") & _lib.FUSED_PATH_RING
         np.testing.assert_array_equal(ref_flags, fn.buffer("flags").get(command_queue))
         flags_t = fn.buffer("flags_t")  # materialised now, filled by the next call
         dev_t = fn.buffer("deviations_t")
@@ -743,18 +729,17 @@ class TestFused:
             fn = template.instantiate(command_queue, 4096, baselines, threshold_args={"n_sigma": 11.0})
             fn.ensure_all_bound()
             fn.buffer("vis").set(command_queue, np.tile(tile, (1, baselines // 64 + 1))[:, :baselines])
-            previous = _lib.call("ksp_flagger_fused_ring_mode", 0)
-            try:
+            with _lib.fused_ring_mode(0):
                 fn()
-                assert bool(_lib.call("ksp_flagger_fused_last_path") & 4) == expect_ring
+                took_ring = bool(_lib.call("ksp_flagger_fused_last_path") & _lib.FUSED_PATH_RING)
+                assert took_ring == expect_ring
                 auto = fn.buffer("flags").get(command_queue), fn.buffer("noise").get(command_queue)
-                _lib.call("ksp_flagger_fused_ring_mode", -1 if expect_ring else 1)
-                fn()
-                assert bool(_lib.call("ksp_flagger_fused_last_path") & 4) != expect_ring
+                with _lib.fused_ring_mode(-1 if expect_ring else 1):
+                    fn()
+                took_ring = bool(_lib.call("ksp_flagger_fused_last_path") & _lib.FUSED_PATH_RING)
+                assert took_ring != expect_ring
                 np.testing.assert_array_equal(fn.buffer("flags").get(command_queue), auto[0])
                 np.testing.assert_array_equal(fn.buffer("noise").get(command_queue), auto[1])
-            finally:
-                _lib.call("ksp_flagger_fused_ring_mode", previous)
 
     def test_unsupported_falls_back_to_sequence(self, context, command_queue):
         from katsdpsigproc_amd.rfi import device

@@ -6,11 +6,10 @@ The reference's rolling median leaves +-inf amplitudes out of every window (pand
 them into NaN first), while their own deviation is inf - median, and 0 when no finite
 sample is left in the window."""
 
-import contextlib
-
 import numpy as np
 import pytest
 
+from katsdpsigproc_amd import _lib
 from tests import inputs
 
 pytestmark = pytest.mark.gpu
@@ -51,22 +50,9 @@ def mode_flags(in_flags, mode, chan_col):
     return {"none": None, "channel": in_flags[:, chan_col], "full": in_flags}[mode]
 
 
-@contextlib.contextmanager
-def ring_mode(mode):
-    """ksp_flagger_fused_ring_mode: 1 forces the ring kernel where it applies, 2 keeps it off."""
-    from katsdpsigproc_amd import _lib
-
-    previous = _lib.call("ksp_flagger_fused_ring_mode", mode)
-    try:
-        yield
-    finally:
-        _lib.call("ksp_flagger_fused_ring_mode", previous)
-
-
 def run_flagger(context, queue, vis, fl, *, width=13, amplitudes=False, noise="MADT",
                 n_windows=4, keep_deviations=True, fused=True, n_sigma=11.0):  # fmt: skip
     """The flagger on `vis`; returns (outputs, ksp_flagger_fused_last_path)."""
-    from katsdpsigproc_amd import _lib
     from katsdpsigproc_amd.rfi import device
 
     mode = "NONE" if fl is None else ("CHANNEL" if fl.ndim == 1 else "FULL")
@@ -120,16 +106,16 @@ class TestFused:
         vis, in_flags, _, rows, chan_col = inputs.nonfinite_input("cplx")
         fl = mode_flags(in_flags, mode, chan_col)
         out, path = run_flagger(context, command_queue, vis, fl, width=width, n_windows=n_windows)
-        assert path == 1, path
+        assert path == _lib.FUSED_PATH_STRIP, path
         check_oracle(oracle, out, vis, fl, width=width, n_windows=n_windows)
         if n_windows == 4:
             check_golden(golden, out, f"cplx_w{width}_{mode}", rows, vis.shape)
 
     def test_ring_kernel(self, context, command_queue, oracle, golden):
         vis, _, _, rows, _ = inputs.nonfinite_input("cplx")
-        with ring_mode(1):
+        with _lib.fused_ring_mode(1):
             out, path = run_flagger(context, command_queue, vis, None, keep_deviations=False)
-        assert path & 4, path
+        assert path & _lib.FUSED_PATH_RING, path
         check_oracle(oracle, out, vis, None)
         check_golden(golden, out, "cplx_w13_none", rows, vis.shape)
 
@@ -145,14 +131,14 @@ class TestFused:
             vis, _ = inputs.nonfinite_case(channels)
             vis[[4095, 4096, 8191, 8192 % channels], 5] = np.inf
         out, path = run_flagger(context, command_queue, vis, None, amplitudes=amplitudes)
-        assert path == 2, path
+        assert path == _lib.FUSED_PATH_LONG, path
         check_oracle(oracle, out, vis, None, amplitudes=amplitudes)
 
     def test_amplitude_input_golden(self, context, command_queue, oracle, golden):
         vis, in_flags, _, rows, _ = inputs.nonfinite_input("amp")
         for mode, fl in (("none", None), ("full", in_flags)):
             out, path = run_flagger(context, command_queue, vis, fl, amplitudes=True)
-            assert path == 1, path
+            assert path == _lib.FUSED_PATH_STRIP, path
             check_oracle(oracle, out, vis, fl, amplitudes=True)
             check_golden(golden, out, f"amp_w13_{mode}", rows, vis.shape)
 

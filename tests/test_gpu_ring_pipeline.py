@@ -8,8 +8,6 @@ and the last chunk of a lane's run of 64 channels, in the strips on either side 
 Width 13, 11 sigma, 4 windows, 4096 channels; the noise is ``generate_data`` of the reference's
 scripts/rfiflagtest.py (``synth_block`` of bench.py)."""
 
-import contextlib
-
 import numpy as np
 import pytest
 
@@ -67,17 +65,6 @@ def noise_block():
     return vis
 
 
-@contextlib.contextmanager
-def force_ring():
-    from katsdpsigproc_amd import _lib
-
-    previous = _lib.call("ksp_flagger_fused_ring_mode", 1)
-    try:
-        yield
-    finally:
-        _lib.call("ksp_flagger_fused_ring_mode", previous)
-
-
 def special_baselines(baselines):
     """Whole strips of 8 baselines at the start, in the middle and at the end of the strips the
     ring kernel takes, strips of even and odd number next to each other: with the strips handed
@@ -120,11 +107,11 @@ def run_ring(context, queue, vis):
     outs = []
     for _ in range(2):
         fn.buffer("flags").set(queue, np.full(vis.shape, 255, np.uint8))
-        with force_ring():
+        with _lib.fused_ring_mode(1):
             fn()
         path = _lib.call("ksp_flagger_fused_last_path")
-        assert path & 4, f"expected the ring kernel, last path = {path}"
-        assert (path & 1) == (1 if vis.shape[1] % 8 else 0), path
+        assert path & _lib.FUSED_PATH_RING, f"expected the ring kernel, last path = {path}"
+        assert bool(path & _lib.FUSED_PATH_STRIP) == bool(vis.shape[1] % 8), path
         outs.append((fn.buffer("flags").get(queue), fn.buffer("noise").get(queue)))
     return outs
 

@@ -19,12 +19,12 @@ The alignment cases, as far as a signature allows them (V = elements per 16 byte
   E  B and C together
 """
 
-import contextlib
 import ctypes
 
 import numpy as np
 import pytest
 
+from katsdpsigproc_amd import _lib
 from tests import inputs, subviews
 
 pytestmark = pytest.mark.gpu
@@ -73,8 +73,6 @@ class Gpu:
         return subviews.DeviceView(self.context, self.queue, dtype, blank, stride, offset)
 
     def call(self, name, *args):
-        from katsdpsigproc_amd import _lib
-
         return _lib.call(name, self.device, self.stream, *args)
 
 
@@ -422,29 +420,19 @@ def test_maskedsum(use_amplitudes, gpu, oracle):
 
 
 # ------------------------------------------------------------------------- fused flagger
-@contextlib.contextmanager
-def ring_mode(mode):
-    from katsdpsigproc_amd import _lib
-
-    previous = _lib.call("ksp_flagger_fused_ring_mode", mode)
-    try:
-        yield
-    finally:
-        _lib.call("ksp_flagger_fused_ring_mode", previous)
-
-
 FUSED_SCALES = (ctypes.c_double * 4)(*[pow(1.2, -i) for i in range(4)])
+STRIP, LONG, RING = _lib.FUSED_PATH_STRIP, _lib.FUSED_PATH_LONG, _lib.FUSED_PATH_RING
 # (channels, baselines, width, deviations output, ring mode, kernels launched, which is ...)
 FUSED_SHAPES = [
-    pytest.param(200, 10, 13, True, 0, 1, id="lanes-of-4"),  # flagger_fused_kernel<4, 13>
+    pytest.param(200, 10, 13, True, 0, STRIP, id="lanes-of-4"),  # flagger_fused_kernel<4, 13>
     # rows wide enough for whole 16-byte pieces in the row-wise zero fill of flags, starting
     # at every alignment (the stride of 75 is odd)
-    pytest.param(200, 70, 13, True, 0, 1, id="lanes-of-4-wide-rows"),
-    pytest.param(1000, 10, 13, True, 0, 1, id="lanes-of-16"),  # <16, 13>
-    pytest.param(4096, 12, 13, False, 1, 5, id="ring"),  # ring kernel + 4 baselines left over
-    pytest.param(4096, 12, 13, True, 0, 1, id="lanes-of-64"),  # <64, 13>
-    pytest.param(600, 10, 21, True, 0, 1, id="width-21"),
-    pytest.param(8192, 6, 13, True, 0, 2, id="long"),  # flagger_long_kernel
+    pytest.param(200, 70, 13, True, 0, STRIP, id="lanes-of-4-wide-rows"),
+    pytest.param(1000, 10, 13, True, 0, STRIP, id="lanes-of-16"),  # <16, 13>
+    pytest.param(4096, 12, 13, False, 1, RING | STRIP, id="ring"),  # ring + 4 baselines left over
+    pytest.param(4096, 12, 13, True, 0, STRIP, id="lanes-of-64"),  # <64, 13>
+    pytest.param(600, 10, 21, True, 0, STRIP, id="width-21"),
+    pytest.param(8192, 6, 13, True, 0, LONG, id="long"),  # flagger_long_kernel
 ]
 
 
@@ -453,7 +441,7 @@ def test_flagger_fused(channels, baselines, width, keep_deviations, ring, path, 
     """`vis` is 16-byte aligned with an even stride, as the ABI requires; every other array is
     a sub-view. `flags` in particular is a column block of a wider array: the zero fill ahead
     of the kernel may clear its rows and nothing between them."""
-    from katsdpsigproc_amd import _lib, accel
+    from katsdpsigproc_amd import accel
 
     vis = inputs.add_rfi(inputs.generate_data(channels, baselines, seed=width), seed=baselines)
     rs = np.random.RandomState(channels)
@@ -480,7 +468,7 @@ def test_flagger_fused(channels, baselines, width, keep_deviations, ring, path, 
         d_dev = gpu.output(vis.shape, F32, baselines + 3) if keep_deviations else None
         workspace = accel.DeviceArray(gpu.context, (16,), np.uint32)  # 64 bytes, zeroed once
         workspace.zero(gpu.queue)
-        with ring_mode(ring):
+        with _lib.fused_ring_mode(ring):
             gpu.call("ksp_flagger_fused", d_vis.ptr, None if d_mask is None else d_mask.ptr,
                      d_flags.ptr, None if d_dev is None else d_dev.ptr, d_noise.ptr, channels,
                      baselines, d_vis.stride, mask_stride, d_flags.stride,

@@ -48,19 +48,19 @@ for r in range(rounds):
         fn.buffer("vis").set(q, vis)
         out = {}
         for ring in ("1", "0"):
-            _lib.call("ksp_flagger_fused_ring_mode", 1 if ring == "1" else -1)
-            for rep in range(3 if ring == "1" else 1):
-                fn.buffer("flags").set(q, np.full((C, B), 255, np.uint8))
-                fn()
-                path = _lib.call("ksp_flagger_fused_last_path")
-                assert bool(path & 4) == (ring == "1"), path
-                got = (fn.buffer("flags").get(q), fn.buffer("noise").get(q))
-                if ring in out:
-                    same = np.array_equal(got[0], out[ring][0]) and np.array_equal(got[1], out[ring][1], equal_nan=True)
-                    if not same:
-                        bad += 1
-                        print("ROUND %d pad %d: the ring kernel's repeat %d differs from its first run" % (r, pad, rep))
-                out[ring] = got
+            with _lib.fused_ring_mode(1 if ring == "1" else -1):
+                for rep in range(3 if ring == "1" else 1):
+                    fn.buffer("flags").set(q, np.full((C, B), 255, np.uint8))
+                    fn()
+                    path = _lib.call("ksp_flagger_fused_last_path")
+                    assert bool(path & _lib.FUSED_PATH_RING) == (ring == "1"), path
+                    got = (fn.buffer("flags").get(q), fn.buffer("noise").get(q))
+                    if ring in out:
+                        same = np.array_equal(got[0], out[ring][0]) and np.array_equal(got[1], out[ring][1], equal_nan=True)
+                        if not same:
+                            bad += 1
+                            print("ROUND %d pad %d: the ring kernel's repeat %d differs from its first run" % (r, pad, rep))
+                    out[ring] = got
         same = np.array_equal(out["1"][0], out["0"][0]) and np.array_equal(out["1"][1], out["0"][1], equal_nan=True)
         if not same:
             bad += 1
@@ -69,6 +69,5 @@ for r in range(rounds):
                   % (r, pad, len(d), d[:1].tolist(), int((out["1"][1] != out["0"][1]).sum())))
         print("round %d (kind %d) pad %2d: flagged %.4f  %s" % (r, kind, pad, float((out["1"][0] != 0).mean()),
                                                               "same" if same else "DIFFERENT"), flush=True)
-_lib.call("ksp_flagger_fused_ring_mode", 0)
 print("stress_ring: %d mismatches" % bad)
 sys.exit(1 if bad else 0)
