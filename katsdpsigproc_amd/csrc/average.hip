@@ -26,7 +26,7 @@
 // Traffic per sample: accumulate reads 8 (vis) + 1 (flags) + 4 (weights) and
 // reads and writes 8 + 4 + 1 of accumulators: 39 bytes, 35 without weights, plus one byte for
 // a FULL mask. finalise reads 13 and, with clear, writes 13, plus 13 / channel_factor out.
-#include "ksp_common.h"
+#include "launch.h"
 
 #define AVG_THREADS 256
 #define AVG_RUN 16
@@ -258,9 +258,10 @@ __global__ __launch_bounds__(AVG_THREADS) void average_finalise_kernel(
     }
 }
 
+// 16-byte accesses to an array's rows; an array that is not given (NULL) does not object
 static bool avg_aligned16(const void *p, long long stride, int itemsize)
 {
-    return p == nullptr || ((uintptr_t)p % 16 == 0 && (stride * itemsize) % 16 == 0);
+    return p == nullptr || ksp_rows_aligned(p, stride, itemsize);
 }
 
 template <bool HAS_W>
@@ -272,21 +273,15 @@ static void avg_launch_accumulate(int mode, dim3 grid, hipStream_t stream, const
                                   int weights_stride, int input_flags_stride, int acc_vis_stride,
                                   int acc_weights_stride, int acc_flags_stride, int aligned)
 {
-#define AVG_CASE(m)                                                                              \
-    case m:                                                                                      \
-        hipLaunchKernelGGL((average_accumulate_kernel<HAS_W, m>), grid, dim3(AVG_THREADS), 0,    \
-                           stream, vis, flags, weights, input_flags, acc_vis, acc_weights,       \
-                           acc_flags, runs, runs_per_row, baselines, (long long)vis_stride,      \
-                           (long long)flags_stride, (long long)weights_stride,                   \
-                           (long long)input_flags_stride, (long long)acc_vis_stride,             \
-                           (long long)acc_weights_stride, (long long)acc_flags_stride, aligned); \
-        break;
-    switch (mode) {
-        AVG_CASE(0)
-        AVG_CASE(1)
-        AVG_CASE(2)
-    }
-#undef AVG_CASE
+    // (mode is 0 .. 2 here)
+    ksp_dispatch_exact<0, 1, 2>(mode, [&](auto MODE) {
+        hipLaunchKernelGGL((average_accumulate_kernel<HAS_W, MODE()>), grid, dim3(AVG_THREADS), 0,
+                           stream, vis, flags, weights, input_flags, acc_vis, acc_weights,
+                           acc_flags, runs, runs_per_row, baselines, (long long)vis_stride,
+                           (long long)flags_stride, (long long)weights_stride,
+                           (long long)input_flags_stride, (long long)acc_vis_stride,
+                           (long long)acc_weights_stride, (long long)acc_flags_stride, aligned);
+    });
 }
 
 extern "C" int ksp_average_accumulate(int device, void *stream, const void *vis,

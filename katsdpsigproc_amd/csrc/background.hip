@@ -232,33 +232,17 @@ extern "C" int ksp_background_median_filter(int device, void *stream, const void
     if (channels == 0 || baselines == 0) return 0;
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
-#define KSP_BG(W)                                                                               \
-    case W:                                                                                     \
-        return launch_background<W>(s, in, out, flags, channels, baselines, stride, flags_stride, \
-                                    is_amplitude, flags_mode, csplit)
     if (width > 31)
         return launch_background_wide_any(s, in, out, flags, channels, baselines, stride,
                                           flags_stride, width, is_amplitude, flags_mode, csplit);
-    switch (width) {
-        KSP_BG(3);
-        KSP_BG(5);
-        KSP_BG(7);
-        KSP_BG(9);
-        KSP_BG(11);
-        KSP_BG(13);
-        KSP_BG(15);
-        KSP_BG(17);
-        KSP_BG(19);
-        KSP_BG(21);
-        KSP_BG(23);
-        KSP_BG(25);
-        KSP_BG(27);
-        KSP_BG(29);
-        KSP_BG(31);
-    default:
-        ksp_set_error("ksp_background_median_filter: width %d has no compiled kernel "
-                      "(available: odd 3..255)", width);
-        return (int)hipErrorInvalidValue;
-    }
-#undef KSP_BG
+    int rc = 0;
+    // odd widths 3 .. 31 arrive here
+    if (ksp_dispatch_exact<3, 5, 7, 9, 11, 13, 15, 17, 19, 21, 23, 25, 27, 29, 31>(width, [&](auto W) {
+            rc = launch_background<W()>(s, in, out, flags, channels, baselines, stride,
+                                        flags_stride, is_amplitude, flags_mode, csplit);
+        }))
+        return rc;
+    ksp_set_error("ksp_background_median_filter: width %d has no compiled kernel "
+                  "(available: odd 3..255)", width);
+    return (int)hipErrorInvalidValue;
 }

@@ -31,7 +31,7 @@
 // initialisation when they are read as leaving samples) plus a copy of its first G slots
 // after the end, so that G consecutive leaving samples are always contiguous.
 #pragma once
-#include "ksp_common.h"
+#include "launch.h"
 
 namespace ksp_bgwide {
 
@@ -220,22 +220,19 @@ static int launch_background_wide(hipStream_t s, const void *in, float *out, con
     return 0;
 }
 
-// Smallest compiled S with G * S >= width + 1.
+// Smallest compiled S with G * S >= width + 1: S = 5 up to width 39, then 63, 127, 191, 255.
 static int launch_background_wide_any(hipStream_t s, const void *in, float *out,
                                       const uint8_t *flags, int channels, int baselines,
                                       int stride, int flags_stride, int width, int is_amplitude,
                                       int flags_mode, int csplit)
 {
-#define KSP_BGW(S_)                                                                           \
-    if (width < ksp_bgwide::G * (S_))                                                        \
-    return launch_background_wide<S_>(s, in, out, flags, channels, baselines, stride,         \
-                                      flags_stride, width, is_amplitude, flags_mode, csplit)
-    KSP_BGW(5);   // widths up to 39
-    KSP_BGW(8);   // 63
-    KSP_BGW(16);  // 127
-    KSP_BGW(24);  // 191
-    KSP_BGW(32);  // 255
-#undef KSP_BGW
+    int rc = 0;
+    // widths 33 .. MAX_WIDTH arrive here: 5 .. 32 slots per lane
+    if (ksp_dispatch_ceil<5, 8, 16, 24, 32>(ksp_divup(width + 1, ksp_bgwide::G), [&](auto S) {
+            rc = launch_background_wide<S()>(s, in, out, flags, channels, baselines, stride,
+                                             flags_stride, width, is_amplitude, flags_mode, csplit);
+        }))
+        return rc;
     ksp_set_error("ksp_background_median_filter: width %d has no compiled kernel", width);
     return (int)hipErrorInvalidValue;
 }

@@ -38,7 +38,7 @@
 // Unaligned input (flags or stride not a multiple of 16) and the lanes at the right-hand
 // edge, where fewer than 16 columns are left, load byte by byte and only bytes inside
 // the row: padding is never read, let alone counted.
-#include "ksp_common.h"
+#include "launch.h"
 
 #define FC_THREADS 256
 #define FC_TILE_COLS (FC_THREADS * 16)
@@ -238,7 +238,7 @@ extern "C" int ksp_flag_count(int device, void *stream, const uint8_t *flags, ui
     const int tile_rows = fc_tile_rows(rows, col_tiles, n_masks);
     const long long tiles = col_tiles * (((long long)rows + tile_rows - 1) / tile_rows);
     KSP_REQUIRE(tiles <= 0x7fffffffll, "array too large for one launch");
-    const int aligned = ((uintptr_t)flags % 16 == 0 && stride % 16 == 0) ? 1 : 0;
+    const int aligned = ksp_rows_aligned(flags, stride, 1);
 
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
@@ -250,23 +250,12 @@ extern "C" int ksp_flag_count(int device, void *stream, const uint8_t *flags, ui
                                    (size_t)n_masks, s));
     }
     const dim3 grid((unsigned)tiles);
-#define FC_CASE(n)                                                                               \
-    case n:                                                                                      \
-        fc_launch<n>(single_bit, grid, s, flags, row_counts, col_counts, rows, cols, stride,     \
-                     row_counts_stride, col_counts_stride, tile_rows, (unsigned)col_tiles,       \
-                     aligned, packed);                                                           \
-        break;
-    switch (n_masks) {
-        FC_CASE(1)
-        FC_CASE(2)
-        FC_CASE(3)
-        FC_CASE(4)
-        FC_CASE(5)
-        FC_CASE(6)
-        FC_CASE(7)
-        FC_CASE(8)
-    }
-#undef FC_CASE
+    // (n_masks is 1 .. FC_MAX_MASKS here)
+    ksp_dispatch_exact<1, 2, 3, 4, 5, 6, 7, 8>(n_masks, [&](auto NM) {
+        fc_launch<NM()>(single_bit, grid, s, flags, row_counts, col_counts, rows, cols, stride,
+                        row_counts_stride, col_counts_stride, tile_rows, (unsigned)col_tiles,
+                        aligned, packed);
+    });
     KSP_LAUNCH_CHECK();
     return 0;
 }

@@ -225,17 +225,16 @@ static FusedPath choose_path(const FusedParams &p, int width, int n_cu, int mode
 static int launch_strip(int lanes, int width, int device, hipStream_t s, const FusedParams &p,
                         hipEvent_t ev0, hipEvent_t ev1)
 {
-#define KSP_WIDTH(W) case W: return ksp_fused_launch_width<W>(device, s, p, ev0, ev1)
-    switch (width) {
-    case 13:
+    if (width == 13) {
         if (lanes == 64) return launch_fused<64, 13>(device, s, p, ev0, ev1);
         if (lanes == 4) return launch_fused<4, 13>(device, s, p, ev0, ev1);
         return launch_fused<16, 13>(device, s, p, ev0, ev1);
-    KSP_WIDTH(3); KSP_WIDTH(5); KSP_WIDTH(7); KSP_WIDTH(9); KSP_WIDTH(11);
-    KSP_WIDTH(15); KSP_WIDTH(17); KSP_WIDTH(19); KSP_WIDTH(21); KSP_WIDTH(23);
-    KSP_WIDTH(25); KSP_WIDTH(27); KSP_WIDTH(29); KSP_WIDTH(31);
     }
-#undef KSP_WIDTH
+    int rc = 0;
+    if (ksp_dispatch_exact<3, 5, 7, 9, 11, 15, 17, 19, 21, 23, 25, 27, 29, 31>(width, [&](auto W) {
+            rc = ksp_fused_launch_width<W()>(device, s, p, ev0, ev1);
+        }))
+        return rc;
     ksp_set_error("fused flagger: width %d is not compiled here", width);
     return (int)hipErrorInvalidValue;
 }

@@ -1,11 +1,34 @@
-// Host-side launch helpers: what a launcher does once per device, and the choice between
-// a plain and an event-timed launch. No device code.
+// Host-side launch helpers: a run-time integer as a template argument, the alignment test of
+// the 16-byte load paths, what a launcher does once per device, and the choice between a
+// plain and an event-timed launch. No device code.
 #pragma once
 #include <hip/hip_ext.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "ksp_common.h"
+
+// A run-time integer as a template argument: f(std::integral_constant<int, V>()) for the V of
+// Vs... that equals `value` (exact), or for the first V that `value` does not exceed (ceil:
+// Vs... ascending). Returns whether there was such a V; f's own result is dropped.
+template <int... Vs, typename F>
+inline bool ksp_dispatch_exact(int value, F &&f)
+{
+    return ((value == Vs && (f(std::integral_constant<int, Vs>()), true)) || ...);
+}
+template <int... Vs, typename F>
+inline bool ksp_dispatch_ceil(int value, F &&f)
+{
+    return ((value <= Vs && (f(std::integral_constant<int, Vs>()), true)) || ...);
+}
+
+// Whether rows that start at `ptr` and lie `stride` elements of `elem_bytes` bytes apart can
+// be read in pieces of `bytes` bytes: every row starts on a multiple of `bytes`.
+inline bool ksp_rows_aligned(const void *ptr, long long stride, int elem_bytes, int bytes = 16)
+{
+    return (uintptr_t)ptr % bytes == 0 && stride * elem_bytes % bytes == 0;
+}
 
 // One value per device, for what is set up or queried once per device: T() means "not yet".
 // A device outside 0 .. 63 has no slot: get() says "not yet" every time and set() does

@@ -174,15 +174,11 @@ extern "C" int ksp_selftest_median_non_zero(int device, void *stream, const floa
                 "bad arguments");
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
-    if (n <= 4 * KSP_RANK_THREADS)
-        hipLaunchKernelGGL(selftest_median_non_zero_kernel<4>, dim3(1), dim3(KSP_RANK_THREADS), 0,
-                           s, data, n, out);
-    else if (n <= 40 * KSP_RANK_THREADS)
-        hipLaunchKernelGGL(selftest_median_non_zero_kernel<40>, dim3(1), dim3(KSP_RANK_THREADS), 0,
-                           s, data, n, out);
-    else
-        hipLaunchKernelGGL(selftest_median_non_zero_kernel<64>, dim3(1), dim3(KSP_RANK_THREADS), 0,
-                           s, data, n, out);
+    // values per thread: 1 .. 64 arrive here (n was checked above)
+    ksp_dispatch_ceil<4, 40, 64>(ksp_divup(n, KSP_RANK_THREADS), [&](auto VT) {
+        hipLaunchKernelGGL(selftest_median_non_zero_kernel<VT()>, dim3(1), dim3(KSP_RANK_THREADS),
+                           0, s, data, n, out);
+    });
     KSP_LAUNCH_CHECK();
     return 0;
 }
@@ -349,7 +345,7 @@ extern "C" int ksp_madnz_t(int device, void *stream, const float *in, float *noi
     hipStream_t s = (hipStream_t)stream;
     if (channels > 64 * KSP_RANK_THREADS) {
         // long rows (madnz_long.h): in LDS up to MADL_STAGE_MAX channels, else streamed
-        const int vec = (stride % 4 == 0) && ((uintptr_t)in % 16 == 0);
+        const int vec = ksp_rows_aligned(in, stride, sizeof(float));
         if (channels <= MADL_STAGE_MAX) {
             const int rc = ksp_lds_opt_in<madnz_t_long_kernel<true>>(
                 device, sizeof(unsigned) * MADL_STAGE_MAX);
@@ -365,40 +361,18 @@ extern "C" int ksp_madnz_t(int device, void *stream, const float *in, float *noi
         return 0;
     }
     if (channels > 1024 && channels <= 4096) {
-        const int vec_ok = (stride % 4 == 0) && ((uintptr_t)in % 16 == 0);
+        const int vec_ok = ksp_rows_aligned(in, stride, sizeof(float));
         hipLaunchKernelGGL(madnz_t_wave_kernel, dim3(ksp_divup(baselines, 4)), dim3(256), 0, s, in,
                            noise, channels, baselines, stride, vec_ok);
         KSP_LAUNCH_CHECK();
         return 0;
     }
-    const int vt = ksp_divup(channels, KSP_RANK_THREADS);
-#define KSP_MT(VT)                                                                             \
-    hipLaunchKernelGGL(madnz_t_kernel<VT>, dim3(baselines), dim3(KSP_RANK_THREADS), 0, s, in, \
-                       noise, channels, stride)
-    if (vt <= 1)
-        KSP_MT(1);
-    else if (vt <= 2)
-        KSP_MT(2);
-    else if (vt <= 4)
-        KSP_MT(4);
-    else if (vt <= 8)
-        KSP_MT(8);
-    else if (vt <= 16)
-        KSP_MT(16);
-    else if (vt <= 24)
-        KSP_MT(24);
-    else if (vt <= 32)
-        KSP_MT(32);
-    else if (vt <= 40)
-        KSP_MT(40);
-    else if (vt <= 64)
-        KSP_MT(64);
-    else {
-        ksp_set_error("ksp_madnz_t: %d channels exceed the supported maximum of %d", channels,
-                      64 * KSP_RANK_THREADS);
-        return (int)hipErrorInvalidValue;
-    }
-#undef KSP_MT
+    // channels per thread: 1 .. 4 (up to 1024 channels) and 17 .. 64 (4097 .. 16384) arrive here
+    ksp_dispatch_ceil<1, 2, 4, 24, 32, 40, 64>(
+        ksp_divup(channels, KSP_RANK_THREADS), [&](auto VT) {
+            hipLaunchKernelGGL(madnz_t_kernel<VT()>, dim3(baselines), dim3(KSP_RANK_THREADS), 0, s,
+                               in, noise, channels, stride);
+        });
     KSP_LAUNCH_CHECK();
     return 0;
 }

@@ -11,6 +11,7 @@
 // HBM-bound at 4 (8 for complex) bytes per element once the search is hidden by
 // other resident workgroups.
 #include "bitplane.h"
+#include "launch.h"
 #include "rank.h"
 
 template <int VT, bool IS_AMP>
@@ -189,62 +190,31 @@ template <bool IS_AMP>
 static int launch_percentile(hipStream_t s, const void *in, float *out, int rows, int in_stride,
                              int out_stride, int first_col, int n_cols)
 {
+    // 16-byte loads (long and wave kernels): every lane's first element 16-byte aligned
+    const int elem = IS_AMP ? 4 : 8, per16 = 16 / elem;
+    const int vec_ok = ksp_rows_aligned(in, in_stride, elem) && (first_col % per16 == 0);
     if (n_cols > 64 * KSP_RANK_THREADS) {
-        // one 1024-thread workgroup per row, VT values per thread (percentile_long.h); the
-        // same 16-byte load rule as the wave kernel
-        const int per16 = IS_AMP ? 4 : 2;
-        const int vec_ok = (in_stride % per16 == 0) && (first_col % per16 == 0) && ((uintptr_t)in % 16 == 0);
-        const int vt = ksp_divup(n_cols, P5L_THREADS);
-#define KSP_P5L(VT)                                                                             \
-    hipLaunchKernelGGL((percentile5_long_kernel<VT, IS_AMP>), dim3(rows), dim3(P5L_THREADS), 0, \
-                       s, in, out, rows, in_stride, out_stride, first_col, n_cols, vec_ok)
-        if (vt <= 32)
-            KSP_P5L(32);
-        else if (vt <= 48)
-            KSP_P5L(48);
-        else
-            KSP_P5L(64);
-#undef KSP_P5L
+        // one 1024-thread workgroup per row, VT values per thread (percentile_long.h):
+        // 17 .. 64 arrive here (16385 .. P5L_MAX_COLUMNS columns)
+        ksp_dispatch_ceil<32, 48, 64>(ksp_divup(n_cols, P5L_THREADS), [&](auto VT) {
+            hipLaunchKernelGGL((percentile5_long_kernel<VT(), IS_AMP>), dim3(rows),
+                               dim3(P5L_THREADS), 0, s, in, out, rows, in_stride, out_stride,
+                               first_col, n_cols, vec_ok);
+        });
         KSP_LAUNCH_CHECK();
         return 0;
     }
     if (n_cols > 1024 && n_cols <= 4096) {
-        // 16-byte loads: every lane's first element 16-byte aligned
-        const int per16 = IS_AMP ? 4 : 2;
-        const int vec_ok = (in_stride % per16 == 0) && (first_col % per16 == 0) && ((uintptr_t)in % 16 == 0);
         hipLaunchKernelGGL((percentile5_wave_kernel<IS_AMP>), dim3(ksp_divup(rows, 4)), dim3(256), 0, s,
                            in, out, rows, in_stride, out_stride, first_col, n_cols, vec_ok);
         KSP_LAUNCH_CHECK();
         return 0;
     }
-    const int vt = ksp_divup(n_cols, KSP_RANK_THREADS);
-#define KSP_P5(VT)                                                                              \
-    hipLaunchKernelGGL((percentile5_kernel<VT, IS_AMP>), dim3(rows), dim3(KSP_RANK_THREADS), 0, \
-                       s, in, out, rows, in_stride, out_stride, first_col, n_cols)
-    if (vt <= 1)
-        KSP_P5(1);
-    else if (vt <= 2)
-        KSP_P5(2);
-    else if (vt <= 4)
-        KSP_P5(4);
-    else if (vt <= 8)
-        KSP_P5(8);
-    else if (vt <= 16)
-        KSP_P5(16);
-    else if (vt <= 24)
-        KSP_P5(24);
-    else if (vt <= 32)
-        KSP_P5(32);
-    else if (vt <= 48)
-        KSP_P5(48);
-    else if (vt <= 64)
-        KSP_P5(64);
-    else {
-        ksp_set_error("ksp_percentile5_float: %d columns exceed the supported maximum of %d",
-                      n_cols, 64 * KSP_RANK_THREADS);
-        return (int)hipErrorInvalidValue;
-    }
-#undef KSP_P5
+    // columns per thread: 1 .. 4 (up to 1024 columns) and 17 .. 64 (4097 .. 16384) arrive here
+    ksp_dispatch_ceil<1, 2, 4, 24, 32, 48, 64>(ksp_divup(n_cols, KSP_RANK_THREADS), [&](auto VT) {
+        hipLaunchKernelGGL((percentile5_kernel<VT(), IS_AMP>), dim3(rows), dim3(KSP_RANK_THREADS),
+                           0, s, in, out, rows, in_stride, out_stride, first_col, n_cols);
+    });
     KSP_LAUNCH_CHECK();
     return 0;
 }

@@ -26,7 +26,7 @@
 // threshold_sum_cm (threshold_cm.h): the same SumThreshold on channel-major deviations
 // ([C][B], no reference counterpart: the reference transposes first), lane <-> baseline,
 // the windows as a streaming pipeline along the channels. Same rules, same flags.
-#include "ksp_common.h"
+#include "launch.h"
 
 // ----------------------------------------------------------------------------
 template <bool TRANSPOSED>
@@ -71,7 +71,7 @@ extern "C" int ksp_threshold_simple(int device, void *stream, const float *devia
     KSP_REQUIRE(rows >= 0 && cols >= 0 && stride >= cols, "bad shape");
     if (rows == 0 || cols == 0) return 0;
     KSP_CHECK(hipSetDevice(device));
-    const int vec_ok = (stride % 4 == 0) && ((uintptr_t)deviations % 16 == 0) &&
+    const int vec_ok = ksp_rows_aligned(deviations, stride, sizeof(float)) &&
                        ((uintptr_t)flags % 4 == 0);
     // grid.y holds at most 65535 rows: larger arrays go in slices
     for (int r0 = 0; r0 < rows; r0 += 65535) {
@@ -248,6 +248,28 @@ __global__ __launch_bounds__(256) void threshold_sum_kernel(
     }
 }
 
+// One launch per slice of baselines, each baseline cut into chunks of 256 * VT channels that
+// overlap by `edge` on either side.
+template <int VT>
+static void launch_threshold_sum(hipStream_t s, const float *deviations, const float *noise,
+                                 uint8_t *flags, int channels, int baselines, int stride,
+                                 float n_sigma, const SumParams &p, int n_windows, int flag_value,
+                                 int edge)
+{
+    const int tot = 256 * VT;
+    const int core = (channels <= tot) ? tot : tot - 2 * edge;
+    const int chunks = ksp_divup(channels, core);
+    const int e = (chunks == 1) ? 0 : edge;
+    // grid.y holds at most 65535 baselines: larger arrays go in slices
+    for (int b0 = 0; b0 < baselines; b0 += 65535) {
+        const int nb = baselines - b0 < 65535 ? baselines - b0 : 65535;
+        hipLaunchKernelGGL(threshold_sum_kernel<VT>, dim3(chunks, nb), dim3(256), 0, s,
+                           deviations + (size_t)b0 * stride, noise + b0,
+                           flags + (size_t)b0 * stride, channels, stride, n_sigma, p, n_windows,
+                           (uint8_t)flag_value, core, e);
+    }
+}
+
 extern "C" int ksp_threshold_sum(int device, void *stream, const float *deviations,
                                  const float *noise, uint8_t *flags, int channels, int baselines,
                                  int stride, float n_sigma, const float *scales, int n_windows,
@@ -264,34 +286,16 @@ extern "C" int ksp_threshold_sum(int device, void *stream, const float *deviatio
     for (int k = 0; k < KSP_MAX_WINDOWS; k++) p.scales[k] = k < n_windows ? scales[k] : 0.0f;
     const int edge = (1 << n_windows) - n_windows - 1;
     hipStream_t s = (hipStream_t)stream;
-#define KSP_TS(VT)                                                                              \
-    do {                                                                                        \
-        const int tot = 256 * VT;                                                               \
-        const int core = (channels <= tot) ? tot : tot - 2 * edge;                        \
-        const int chunks = ksp_divup(channels, core);                                            \
-        const int e = (chunks == 1) ? 0 : edge;                                                  \
-        /* grid.y holds at most 65535 baselines: larger arrays go in slices */                  \
-        for (int b0 = 0; b0 < baselines; b0 += 65535) {                                          \
-            const int nb = baselines - b0 < 65535 ? baselines - b0 : 65535;                      \
-            hipLaunchKernelGGL(threshold_sum_kernel<VT>, dim3(chunks, nb), dim3(256), 0, s,      \
-                               deviations + (size_t)b0 * stride, noise + b0,                     \
-                               flags + (size_t)b0 * stride, channels, stride, n_sigma, p,        \
-                               n_windows, (uint8_t)flag_value, core, e);                         \
-        }                                                                                        \
-    } while (0)
     // vt = channels per thread (8, 16 or 32: chunks of 2048, 4096 or 8192 channels); 0: the
     // smallest that holds the baseline in one chunk (no halo), 32 beyond that
     KSP_REQUIRE(vt == 0 || vt == 8 || vt == 16 || vt == 32, "vt must be 0, 8, 16 or 32");
     if (vt == 0) vt = channels <= 256 * 8 ? 8 : channels <= 256 * 16 ? 16 : 32;
-    const int edge_all = (1 << n_windows) - n_windows - 1;
-    KSP_REQUIRE(channels <= 256 * vt || 256 * vt > 2 * edge_all, "chunk shorter than its halo");
-    if (vt == 8)
-        KSP_TS(8);
-    else if (vt == 16)
-        KSP_TS(16);
-    else
-        KSP_TS(32);
-#undef KSP_TS
+    KSP_REQUIRE(channels <= 256 * vt || 256 * vt > 2 * edge, "chunk shorter than its halo");
+    // (vt is 8, 16 or 32 here)
+    ksp_dispatch_exact<8, 16, 32>(vt, [&](auto VT) {
+        launch_threshold_sum<VT()>(s, deviations, noise, flags, channels, baselines, stride,
+                                   n_sigma, p, n_windows, flag_value, edge);
+    });
     KSP_LAUNCH_CHECK();
     return 0;
 }

@@ -229,23 +229,12 @@ extern "C" int ksp_threshold_sum_cm(int device, void *stream, const float *devia
     KSP_REQUIRE(segments <= 65535, "too many channel segments");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(groups, segments);
-    switch (n_windows) {
-#define KSP_TSCM(N)                                                                             \
-    case N:                                                                                     \
-        hipLaunchKernelGGL(threshold_sum_cm_kernel<N>, grid, dim3(64), 0, s, deviations, noise, \
-                           flags, channels, baselines, stride, n_sigma, p,                      \
-                           (uint8_t)flag_value, core);                                          \
-        break;
-        KSP_TSCM(1)
-        KSP_TSCM(2)
-        KSP_TSCM(3)
-        KSP_TSCM(4)
-        KSP_TSCM(5)
-        KSP_TSCM(6)
-        KSP_TSCM(7)
-        KSP_TSCM(8)
-#undef KSP_TSCM
-    }
+    // (n_windows is 1 .. KSP_MAX_WINDOWS here)
+    ksp_dispatch_exact<1, 2, 3, 4, 5, 6, 7, 8>(n_windows, [&](auto N) {
+        hipLaunchKernelGGL(threshold_sum_cm_kernel<N()>, grid, dim3(64), 0, s, deviations, noise,
+                           flags, channels, baselines, stride, n_sigma, p, (uint8_t)flag_value,
+                           core);
+    });
     KSP_LAUNCH_CHECK();
     return 0;
 }

@@ -7,7 +7,7 @@
 // conflict-free. Workgroups are enumerated along the *output* rows first so that
 // consecutive blocks (which land on different XCDs) write neighbouring lines.
 // HBM-bound: 2 * elem_size bytes per element.
-#include "ksp_common.h"
+#include "launch.h"
 
 template <typename T, int V>
 __global__ __launch_bounds__(256) void transpose_kernel(T *__restrict__ dst,
@@ -92,10 +92,8 @@ extern "C" int ksp_transpose(int device, void *stream, void *dst, const void *sr
     hipStream_t s = (hipStream_t)stream;
     // The vector path needs 16-byte (or V*elem) aligned row starts on both sides.
     auto aligned = [&](int v) {
-        size_t bytes = (size_t)v * elem_size;
-        return ((uintptr_t)dst % bytes == 0) && ((uintptr_t)src % bytes == 0) &&
-               ((size_t)in_stride * elem_size % bytes == 0) &&
-               ((size_t)out_stride * elem_size % bytes == 0);
+        return ksp_rows_aligned(dst, out_stride, elem_size, v * elem_size) &&
+               ksp_rows_aligned(src, in_stride, elem_size, v * elem_size);
     };
     switch (elem_size) {
     case 1:

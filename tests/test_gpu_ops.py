@@ -43,6 +43,13 @@ def pad_dimension(dim, extra):
     accel.Dimension(dim.size, min_padded_size=dim.size + extra).link(dim)
 
 
+# Row lengths at which the baseline-major noise estimate and percentile5 change kernel or
+# template instantiation (1, 2, 4 values per thread up to 1024, the wavefront kernel up to 4096,
+# then 24, 32, 40 / 48 and 64 values per thread): the smallest and the largest of each.
+ROW_LENGTH_EDGES = [1, 256, 257, 512, 513, 1024, 1025, 4096, 4097, 6144, 6145, 8192, 8193, 10240,
+                    10241, 12288, 12289, 16384]  # fmt: skip
+
+
 def unpack(bits, shape):
     n = int(np.prod(shape))
     return np.unpackbits(bits)[:n].reshape(shape).astype(np.uint8)
@@ -99,7 +106,8 @@ class TestPercentile5:
             (4092, 4032, True, None),
             (4096, 4096, True, None),  # BASELINE config 2, exactly
             (7, 16384, True, None),
-        ],
+        ]
+        + [(3, C, is_amplitude, None) for C in ROW_LENGTH_EDGES for is_amplitude in (True, False)],
     )
     def test_percentile5(self, R, C, is_amplitude, column_range, context, command_queue, oracle):
         # reference test/test_percentile.py:37-90 (+ one maximum-width case)
@@ -315,7 +323,8 @@ class TestNoiseEst:
                                        # the reference script's presets (rfiflagtest.py:190-195)
                                        (8192, 21), (10240, 70), (8191, 3), (6000, 5),
                                        (16384, 4),
-                                       (4096, 8192)])  # BASELINE config 3, exactly  # fmt: skip
+                                       (4096, 8192)]  # BASELINE config 3, exactly
+                                      + [(channels, 3) for channels in ROW_LENGTH_EDGES])  # fmt: skip
     def test_result(self, kind, shape, context, command_queue, oracle):
         # reference test/rfi/test_noise_est.py:54-79; exact instead of rtol 1e-7
         from katsdpsigproc_amd.rfi import device

@@ -9,7 +9,9 @@ from tests import inputs
 
 pytestmark = pytest.mark.gpu
 
-WIDTHS = [16385, 16448, 20000, 32767, 32768, 40001, 65535, 65536]
+# among them the smallest and the largest width of every kernel instantiation (32, 48 and 64
+# values per thread: up to 32768, 49152, 65536)
+WIDTHS = [16385, 16448, 20000, 32767, 32768, 32769, 40001, 49152, 49153, 65535, 65536]
 
 
 @pytest.fixture(scope="module")

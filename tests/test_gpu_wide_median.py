@@ -61,7 +61,9 @@ def check(oracle, out, vis, flags=None, width=63, amplitudes=False):
         np.testing.assert_array_equal(expected.astype(np.float32), out)
 
 
-WIDTHS = [33, 35, 63, 65, 127, 129, 191, 255]
+# the smallest and the largest width of every kernel instantiation (5, 8, 16, 24 and 32 slots
+# per lane: up to 39, 63, 127, 191, 255), and 35
+WIDTHS = [33, 35, 39, 41, 63, 65, 127, 129, 191, 193, 255]
 
 
 class TestWideBackground:
