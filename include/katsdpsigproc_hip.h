@@ -419,6 +419,24 @@ int ksp_average_finalise(int device, void *stream, void *acc_vis, float *acc_wei
                          int acc_flags_stride, int out_vis_stride, int out_weights_stride,
                          int out_flags_stride);
 
+/* sir: the scale-invariant rank operator along one axis of flags [rows][stride] uint8, in
+ * place (no reference counterpart; bit for bit what rfi/host.py ScaleInvariantRankHost
+ * computes). axis 0: a line is a column, `cols` lines of `rows` samples (the flagger's
+ * channels x baselines output); axis 1: a line is a row, `rows` lines of `cols` samples (the
+ * baselines x channels layout). A line has 1 .. 262144 samples. A sample is flagged when
+ * flags & mask != 0. With psi = eta_q for a flagged sample and eta_q - 4096 for any other, and
+ * M(j) the sum of psi over the first j samples of the line (int32), sample x is in the result
+ * iff max over b in (x, n] of M(b) >= min over a in [0, x] of M(a): x lies in an interval
+ * [a, b) with 4096 * #flagged(a, b) >= (4096 - eta_q) * (b - a). Every sample of the result
+ * gets flags |= flag_value; every other bit of every byte is kept. The result contains the
+ * input; eta_q = 0 (0 .. 4096 allowed) adds nothing, 4096 flags everything. mask and
+ * flag_value are 1 .. 255 and may overlap. Row offsets are 64-bit; bytes between cols and
+ * stride are never read and never written. flags or stride that are odd (axis 0, also an odd
+ * cols) or not multiples of 16 (axis 1) take a slower, byte-wise path with the same result.
+ * No workspace. Every argument is checked before any device call. */
+int ksp_sir(int device, void *stream, uint8_t *flags, int rows, int cols, int stride, int axis,
+            int eta_q, int mask, int flag_value);
+
 /* ---- masked_gaussian_filter (reference rfi/twodflag.py:254-400) ----
  * Images [images][rows][cols] of float32 (itemsize 4) or float64 (itemsize 8); data, flags
  * (uint8, non-zero = flagged) and out share image_stride and row_stride, in elements

@@ -173,6 +173,7 @@ SIGNATURES = {
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
         c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
     ],
+    "ksp_sir": [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int],
     "ksp_launch_function": [
         c_int, c_void_p, c_void_p, POINTER(ctypes.c_uint), POINTER(ctypes.c_uint), ctypes.c_uint,
         POINTER(c_void_p),

@@ -253,6 +253,32 @@ __device__ __forceinline__ int ksp_wave_scan_dpp(int v)
     return v;
 }
 
+// Inclusive prefix minimum / maximum over the lanes of a wavefront, the same network. A lane
+// that a step gives no source (the first lanes of a row, the rows a row mask leaves out)
+// receives the identity instead of the zero that suits a sum.
+#define KSP_DPP_OR(v, identity, ctrl, rows) \
+    __builtin_amdgcn_update_dpp(identity, (int)(v), ctrl, rows, 0xf, false)
+__device__ __forceinline__ int ksp_wave_scan_min_dpp(int v)
+{
+    v = min(v, KSP_DPP_OR(v, 0x7fffffff, 0x111, 0xf));
+    v = min(v, KSP_DPP_OR(v, 0x7fffffff, 0x112, 0xf));
+    v = min(v, KSP_DPP_OR(v, 0x7fffffff, 0x114, 0xf));
+    v = min(v, KSP_DPP_OR(v, 0x7fffffff, 0x118, 0xf));
+    v = min(v, KSP_DPP_OR(v, 0x7fffffff, 0x142, 0xa));
+    v = min(v, KSP_DPP_OR(v, 0x7fffffff, 0x143, 0xc));
+    return v;
+}
+__device__ __forceinline__ int ksp_wave_scan_max_dpp(int v)
+{
+    v = max(v, KSP_DPP_OR(v, -0x7fffffff - 1, 0x111, 0xf));
+    v = max(v, KSP_DPP_OR(v, -0x7fffffff - 1, 0x112, 0xf));
+    v = max(v, KSP_DPP_OR(v, -0x7fffffff - 1, 0x114, 0xf));
+    v = max(v, KSP_DPP_OR(v, -0x7fffffff - 1, 0x118, 0xf));
+    v = max(v, KSP_DPP_OR(v, -0x7fffffff - 1, 0x142, 0xa));
+    v = max(v, KSP_DPP_OR(v, -0x7fffffff - 1, 0x143, 0xc));
+    return v;
+}
+
 __device__ __forceinline__ unsigned ksp_wave_or_dpp(unsigned u)
 {
     int v = (int)u;

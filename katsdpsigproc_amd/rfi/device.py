@@ -1373,6 +1373,132 @@ class FlagCountHostFromDevice:
                 fn.buffer("baseline_counts").get(self.command_queue))  # fmt: skip
 
 
+# ------------------------------------------------------------ scale-invariant rank
+SIR_MAX_CHANNELS = 262144
+
+
+class ScaleInvariantRankTemplate:
+    """Scale-invariant rank (SIR) extension of flags along the channel axis, in place, on the
+    device (no reference counterpart); see :class:`host.ScaleInvariantRankHost` for the rule,
+    which the kernels match bit for bit.
+
+    It belongs between a flagger and whatever consumes its flags (:class:`FlagCount`,
+    :class:`Accumulate`): all of them have a ``flags`` slot of the same shape, to be shared
+    through the ``compounds`` of an :class:`.accel.OperationSequence`.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    eta, mask, flag_value
+        As for :class:`host.ScaleInvariantRankHost` (same errors). ``eta_q`` is the quantised
+        `eta` the kernel gets.
+    transposed
+        ``False`` (default): `flags` is channels x baselines, the flagger's output.
+        ``True``: baselines x channels, the layout of ``ThresholdSum(transposed=True)``.
+        Channels are the axis of the operator either way.
+    tuning
+        The kernels pick their launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.ScaleInvariantRankHost
+
+    def __init__(self, context: AbstractContext, eta: float, mask: int = 0xFF,
+                 flag_value: int = 1, transposed: bool = False,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        checked = host.ScaleInvariantRankHost(eta, mask, flag_value)
+        self.context = context
+        self.eta = checked.eta
+        self.eta_q = checked.eta_q
+        self.mask = checked.mask
+        self.flag_value = checked.flag_value
+        self.transposed = bool(transposed)
+        self.tuning = tune.fixed_geometry("ScaleInvariantRankTemplate", tuning, ())
+        self.kernel = context.native_kernel("ksp_sir")
+
+    @classmethod
+    def autotune(cls, context: AbstractContext) -> Mapping[str, Any]:
+        """Nothing to search."""
+        return {}
+
+    def instantiate(self, command_queue: AbstractCommandQueue, channels: int, baselines: int,
+                    allocator: Optional[AbstractAllocator] = None) -> "ScaleInvariantRank":  # fmt: skip
+        return ScaleInvariantRank(self, command_queue, channels, baselines, allocator)
+
+
+class ScaleInvariantRank(accel.Operation):
+    """Concrete :class:`ScaleInvariantRankTemplate` (``ValueError`` if `channels` or
+    `baselines` is below 1, or `channels` above 262144).
+
+    .. rubric:: Slots
+
+    **flags** : channels x baselines (baselines x channels if transposed), uint8, in and out
+    """
+
+    def __init__(self, template: ScaleInvariantRankTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(command_queue, allocator)
+        if channels < 1 or baselines < 1:
+            raise ValueError("channels and baselines must be at least 1")
+        if channels > SIR_MAX_CHANNELS:
+            raise ValueError(f"at most {SIR_MAX_CHANNELS} channels")
+        self.template = template
+        self.kernel = template.kernel
+        self.channels = channels
+        self.baselines = baselines
+        self.transposed = template.transposed
+        shape = (baselines, channels) if self.transposed else (channels, baselines)
+        self.slots["flags"] = accel.IOSlot((shape[0], accel.Dimension(shape[1])), np.uint8)
+
+    def _run(self) -> None:
+        flags = self.buffer("flags")
+        self.command_queue.enqueue_kernel(
+            self.kernel,
+            [
+                flags.buffer,
+                np.int32(flags.shape[0]),
+                np.int32(flags.shape[1]),
+                np.int32(flags.padded_shape[1]),
+                np.int32(1 if self.transposed else 0),  # the axis the lines run along
+                np.int32(self.template.eta_q),
+                np.int32(self.template.mask),
+                np.int32(self.template.flag_value),
+            ],
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        return {
+            "eta_q": self.template.eta_q,
+            "mask": self.template.mask,
+            "flag_value": self.template.flag_value,
+            "transposed": self.transposed,
+            "channels": self.channels,
+            "baselines": self.baselines,
+        }
+
+
+class ScaleInvariantRankHostFromDevice:
+    """Make a :class:`ScaleInvariantRankTemplate` callable like
+    :class:`host.ScaleInvariantRankHost`: channel-major `flags` in, a new array out;
+    allocates on every call."""
+
+    def __init__(self, template: ScaleInvariantRankTemplate,
+                 command_queue: AbstractCommandQueue) -> None:  # fmt: skip
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, flags: np.ndarray) -> np.ndarray:
+        channels, baselines = flags.shape
+        fn = self.template.instantiate(self.command_queue, channels, baselines)
+        fn.ensure_all_bound()
+        fn.buffer("flags").set(self.command_queue, flags.T if self.template.transposed else flags)
+        fn()
+        out = fn.buffer("flags").get(self.command_queue)
+        return np.ascontiguousarray(out.T) if self.template.transposed else out
+
+
 # -------------------------------------------------------------------------- averaging
 def _check_average_shape(channels: int, baselines: int, channel_factor: int = 1) -> None:
     if channels < 1 or baselines < 1:

@@ -229,6 +229,72 @@ class FlagCountHost:
         return channel_counts, baseline_counts
 
 
+def check_flag_byte(name: str, value) -> int:
+    """`value` as an int in 1..255 (``ValueError`` otherwise, ``TypeError`` for a value that
+    is not an integer), as :func:`check_flag_masks` checks a mask."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise TypeError(f"{name} {value!r} is not an integer")
+    if not 1 <= value <= 255:
+        raise ValueError(f"{name} {value} is outside 1..255")
+    return int(value)
+
+
+class ScaleInvariantRankHost:
+    """Scale-invariant rank (SIR) operator along the channel axis: extends the flags of
+    every baseline over the gaps between them (Offringa, van de Gronde & Roerdink 2012).
+
+    A sample counts as flagged when ``flags & mask != 0``. Every sample of every channel
+    interval ``[a, b)`` of a baseline with
+
+        ``4096 * #flagged(a, b) >= (4096 - eta_q) * (b - a)``
+
+    is in the result and gets ``flags |= flag_value``; every other bit of every byte is kept.
+    ``eta_q = floor(eta * 4096 + 0.5)`` quantises `eta` once, so that all arithmetic is
+    integer and the device operation (:class:`.device.ScaleInvariantRankTemplate`) matches
+    this class bit for bit. The result contains the input; ``eta = 0`` adds nothing,
+    ``eta = 1`` flags every sample, those of a baseline without any flag included. No
+    reference counterpart.
+
+    The implementation is the running-sum form of the rule: with ``psi = eta_q`` for a
+    flagged sample and ``eta_q - 4096`` for any other, and ``M(j)`` the sum of ``psi`` over the
+    channels below ``j``, channel ``x`` is in the result iff the largest ``M(b)``,
+    ``x < b <= channels``, is at least the smallest ``M(a)``, ``0 <= a <= x``.
+
+    Parameters
+    ----------
+    eta
+        Aggressiveness in [0, 1] (``ValueError`` outside it or for NaN): an interval is
+        flagged when at most that share of it, quantised, is unflagged
+    mask
+        Which bits make a sample count as flagged, 1..255 (``ValueError`` outside,
+        ``TypeError`` for a non-integer); default any
+    flag_value
+        Bits set in every sample of the result, 1..255 (as `mask`); may overlap `mask`
+    """
+
+    def __init__(self, eta: float, mask: int = 0xFF, flag_value: int = 1) -> None:
+        eta = float(eta)
+        if not 0.0 <= eta <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError(f"eta {eta} is outside [0, 1]")
+        self.eta = eta
+        self.eta_q = int(np.floor(eta * 4096.0 + 0.5))
+        self.mask = check_flag_byte("mask", mask)
+        self.flag_value = check_flag_byte("flag_value", flag_value)
+
+    def __call__(self, flags: np.ndarray) -> np.ndarray:
+        """A new channels x baselines uint8 array: `flags` with the result ORed in."""
+        flags = np.asarray(flags)
+        if flags.ndim != 2 or flags.dtype != np.uint8:
+            raise ValueError("flags must be a 2-D uint8 array")
+        flagged = (flags & np.uint8(self.mask)) != 0
+        psi = np.where(flagged, np.int64(self.eta_q), np.int64(self.eta_q - 4096))
+        m = np.zeros((flags.shape[0] + 1, flags.shape[1]), np.int64)
+        np.cumsum(psi, axis=0, out=m[1:])
+        lowest = np.minimum.accumulate(m[:-1], axis=0)  # over a in [0, x]
+        highest = np.maximum.accumulate(m[:0:-1], axis=0)[::-1]  # over b in (x, channels]
+        return flags | np.where(highest >= lowest, np.uint8(self.flag_value), np.uint8(0))
+
+
 class AveragerHost:
     """Flag-aware averaging of visibilities over dumps and over groups of channels.
 
