@@ -4,11 +4,11 @@ from typing import Any, Mapping, Optional, Tuple
 
 import numpy as np
 
-from . import accel, tune
+from . import _native_op, accel
 from .abc import AbstractCommandQueue, AbstractContext
 
 
-class MaskedSumTemplate:
+class MaskedSumTemplate(_native_op.NativeTemplate):
     """``dest[col] = sum_row mask[row] * src[row, col]`` (or of ``abs(src)``).
 
     Parameters
@@ -22,19 +22,13 @@ class MaskedSumTemplate:
         any other key is a ``ValueError`` (:func:`.tune.fixed_geometry`).
     """
 
+    KERNEL = "ksp_maskedsum_float"
     TUNING_KEYS = ("size",)
 
     def __init__(self, context: AbstractContext, use_amplitudes: bool = False,
                  tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
-        self.context = context
         self.use_amplitudes = use_amplitudes
-        self.tuning = tune.fixed_geometry("MaskedSumTemplate", tuning, self.TUNING_KEYS)
-        self.kernel = context.native_kernel("ksp_maskedsum_float")
-
-    @classmethod
-    def autotune(cls, context: AbstractContext, use_amplitudes: bool) -> Mapping[str, Any]:
-        """Nothing to search (reference maskedsum.py:73 times size)."""
-        return {}
+        self._setup(context, tuning)
 
     def instantiate(self, command_queue: AbstractCommandQueue, shape: Tuple[int, int],
                     allocator: Optional[accel.AbstractAllocator] = None) -> "MaskedSum":  # fmt: skip

@@ -4,7 +4,7 @@ from typing import Any, Mapping, Optional, Tuple
 
 import numpy as np
 
-from . import accel, tune
+from . import _native_op, accel
 from .abc import AbstractCommandQueue, AbstractContext
 
 #: the gfx950 kernels keep a row in registers: up to 16384 columns in 256 work-items, longer
@@ -12,7 +12,7 @@ from .abc import AbstractCommandQueue, AbstractContext
 MAX_COLUMNS_SUPPORTED = 1024 * 64
 
 
-class Percentile5Template:
+class Percentile5Template(_native_op.NativeTemplate):
     """Percentiles [0, 100, 25, 75, 50] of each row, "lower" element, no interpolation.
 
     WARNING: assumes all values are positive (as the reference does). Rows of more than
@@ -32,22 +32,16 @@ class Percentile5Template:
         accepted without effect, any other key is a ``ValueError`` (:func:`.tune.fixed_geometry`).
     """
 
+    KERNEL = "ksp_percentile5_float"
     TUNING_KEYS = ("size", "wgsy")
 
     def __init__(self, context: AbstractContext, max_columns: int, is_amplitude: bool = True,
                  tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
         if max_columns > MAX_COLUMNS_SUPPORTED:
             raise ValueError(f"max_columns exceeds {MAX_COLUMNS_SUPPORTED}")
-        self.context = context
         self.max_columns = max_columns
         self.is_amplitude = is_amplitude
-        self.tuning = tune.fixed_geometry("Percentile5Template", tuning, self.TUNING_KEYS)
-        self.kernel = context.native_kernel("ksp_percentile5_float")
-
-    @classmethod
-    def autotune(cls, context, max_columns: int, is_amplitude: bool) -> Mapping[str, Any]:
-        """Nothing to search (reference percentile.py:88-121 times size/wgsy)."""
-        return {}
+        self._setup(context, tuning)
 
     def instantiate(self, command_queue: AbstractCommandQueue, shape: Tuple[int, int],
                     column_range: Optional[Tuple[int, int]] = None,

@@ -19,12 +19,25 @@ from typing import Any, List, Mapping, Optional, Tuple, Type, Union
 
 import numpy as np
 
-from .. import accel, transpose, tune
+from .. import _lib, _native_op, accel, transpose, tune
 from ..abc import AbstractCommandQueue, AbstractContext
 from ..accel import AbstractAllocator
 from . import BackgroundFlags, host
 
 _THRESHOLD_SUM_DEFAULT_THRESHOLD_FALLOFF = 1.2
+
+
+def ctypes_float_array(values):
+    return (ctypes.c_float * len(values))(*[float(v) for v in values])
+
+
+def ctypes_double_array(values):
+    return (ctypes.c_double * len(values))(*[float(v) for v in values])
+
+
+def _check_shape(channels: int, baselines: int) -> None:
+    if channels < 1 or baselines < 1:
+        raise ValueError("channels and baselines must be at least 1")
 
 
 # ----------------------------------------------------------------- abstract interfaces
@@ -89,21 +102,15 @@ class BackgroundHostFromDevice(host.AbstractBackgroundHost):
         self.command_queue = command_queue
 
     def __call__(self, vis: np.ndarray, flags: Optional[np.ndarray] = None) -> np.ndarray:
-        if flags is not None and not self.template.use_flags:
-            raise TypeError("flags were provided but not included in the template")
-        if flags is None and self.template.use_flags:
-            raise TypeError("flags were expected but not provided")
+        _native_op.check_optional(flags, self.template.use_flags, "flags")
         channels, baselines = vis.shape
         fn = self.template.instantiate(self.command_queue, channels, baselines)
-        fn.ensure_all_bound()
-        fn.buffer("vis").set(self.command_queue, vis)
-        if flags is not None:
-            fn.buffer("flags").set(self.command_queue, flags)
-        fn()
-        return fn.buffer("deviations").get(self.command_queue)
+        inputs = {"vis": vis, "flags": flags}
+        return _native_op.run_once(fn, self.command_queue, inputs, ["deviations"])[0]
 
 
-class BackgroundMedianFilterDeviceTemplate(AbstractBackgroundDeviceTemplate):
+class BackgroundMedianFilterDeviceTemplate(_native_op.AutotunedTuning,
+                                           AbstractBackgroundDeviceTemplate):  # fmt: skip
     """Median-filter backgrounder (reference rfi/device.py:141-262).
 
     Unlike the reference kernel, which uses ``hypot`` and float32 throughout and so "may
@@ -148,18 +155,8 @@ class BackgroundMedianFilterDeviceTemplate(AbstractBackgroundDeviceTemplate):
         self.width = width
         self.is_amplitude = is_amplitude
         self.use_flags = use_flags
-        # resolved on first use: a template that only ever feeds the fused flagger
-        # never launches this kernel and should not spend a second tuning it
-        self._tuning = dict(tuning) if tuning is not None else None
+        self._init_tuning(tuning, width, is_amplitude, use_flags)
         self.kernel = context.native_kernel("ksp_background_median_filter")
-
-    @property
-    def tuning(self) -> Mapping[str, Any]:
-        if self._tuning is None:
-            self._tuning = dict(
-                self.autotune(self.context, self.width, self.is_amplitude, self.use_flags)
-            )
-        return self._tuning
 
     @classmethod
     @tune.autotuner(test={"wgs": 64, "csplit": 4})
@@ -203,7 +200,7 @@ class BackgroundMedianFilterDeviceTemplate(AbstractBackgroundDeviceTemplate):
         return BackgroundMedianFilterDevice(self, command_queue, channels, baselines, allocator)
 
 
-class BackgroundMedianFilterDevice(AbstractBackgroundDevice):
+class BackgroundMedianFilterDevice(_native_op.NativeOperation, AbstractBackgroundDevice):
     """Concrete :class:`BackgroundMedianFilterDeviceTemplate`.
 
     .. rubric:: Slots
@@ -216,11 +213,7 @@ class BackgroundMedianFilterDevice(AbstractBackgroundDevice):
     def __init__(self, template: BackgroundMedianFilterDeviceTemplate,
                  command_queue: AbstractCommandQueue, channels: int, baselines: int,
                  allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
-        super().__init__(command_queue, allocator)
-        self.template = template
-        self.kernel = template.kernel
-        self.channels = channels
-        self.baselines = baselines
+        super().__init__(template, command_queue, channels, baselines, allocator)
         vis_type = np.float32 if template.is_amplitude else np.complex64
         # one Dimension object shared by vis, deviations and full flags: equal strides,
         # as in the reference (rfi/device.py:303-307)
@@ -238,31 +231,26 @@ class BackgroundMedianFilterDevice(AbstractBackgroundDevice):
         mode = self.template.use_flags
         flags = self.buffer("flags") if mode else None
         flags_stride = flags.padded_shape[1] if mode == BackgroundFlags.FULL else 0
-        self.command_queue.enqueue_kernel(
-            self.kernel,
-            [
-                vis.buffer,
-                deviations.buffer,
-                flags.buffer if flags is not None else None,
-                np.int32(self.channels),
-                np.int32(self.baselines),
-                np.int32(vis.padded_shape[1]),
-                np.int32(flags_stride),
-                np.int32(self.template.width),
-                np.int32(self.template.is_amplitude),
-                np.int32(mode.value),
-                np.int32(self.template.tuning.get("csplit", 0)),
-            ],
+        self._launch(
+            vis.buffer,
+            deviations.buffer,
+            flags.buffer if flags is not None else None,
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(vis.padded_shape[1]),
+            np.int32(flags_stride),
+            np.int32(self.template.width),
+            np.int32(self.template.is_amplitude),
+            np.int32(mode.value),
+            np.int32(self.template.tuning.get("csplit", 0)),
         )
 
     def parameters(self) -> Mapping[str, Any]:
-        return {
-            "width": self.template.width,
-            "use_flags": self.template.use_flags.name,
-            "csplit": self.template.tuning.get("csplit", 0),
-            "channels": self.channels,
-            "baselines": self.baselines,
-        }
+        return self._parameters(
+            width=self.template.width,
+            use_flags=self.template.use_flags.name,
+            csplit=self.template.tuning.get("csplit", 0),
+        )
 
 
 # ------------------------------------------------------------------------------ noise
@@ -276,16 +264,13 @@ class NoiseEstHostFromDevice(host.AbstractNoiseEstHost):
 
     def __call__(self, deviations: np.ndarray) -> np.ndarray:
         channels, baselines = deviations.shape
+        fn = self.template.instantiate(self.command_queue, channels, baselines)
         if self.template.transposed:
             deviations = deviations.T
-        fn = self.template.instantiate(self.command_queue, channels, baselines)
-        fn.ensure_all_bound()
-        fn.buffer("deviations").set(self.command_queue, deviations)
-        fn()
-        return fn.buffer("noise").get(self.command_queue)
+        return _native_op.run_once(fn, self.command_queue, {"deviations": deviations}, ["noise"])[0]
 
 
-class NoiseEstMADDeviceTemplate(AbstractNoiseEstDeviceTemplate):
+class NoiseEstMADDeviceTemplate(_native_op.AutotunedTuning, AbstractNoiseEstDeviceTemplate):
     """Median of non-zero absolute deviations on channel-major data
     (reference rfi/device.py:363-409). :class:`NoiseEstMADTDeviceTemplate` is faster, as
     the reference also notes (rfi/device.py:366).
@@ -304,16 +289,10 @@ class NoiseEstMADDeviceTemplate(AbstractNoiseEstDeviceTemplate):
     def __init__(self, context: AbstractContext,
                  tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
         self.context = context
-        self._tuning = dict(tuning) if tuning is not None else None  # resolved on first use
+        self._init_tuning(tuning)
         self.kernel = context.native_kernel("ksp_madnz")
         self.kernel_t = context.native_kernel("ksp_madnz_t")
         self.kernel_transpose = context.native_kernel("ksp_transpose")
-
-    @property
-    def tuning(self) -> Mapping[str, Any]:
-        if self._tuning is None:
-            self._tuning = dict(self.autotune(self.context))
-        return self._tuning
 
     @classmethod
     @tune.autotuner(test={"method": 0})
@@ -336,7 +315,7 @@ class NoiseEstMADDeviceTemplate(AbstractNoiseEstDeviceTemplate):
         return NoiseEstMADDevice(self, command_queue, channels, baselines, allocator)
 
 
-class NoiseEstMADDevice(AbstractNoiseEstDevice):
+class NoiseEstMADDevice(_native_op.NativeOperation, AbstractNoiseEstDevice):
     """Concrete :class:`NoiseEstMADDeviceTemplate`.
 
     .. rubric:: Slots
@@ -357,11 +336,7 @@ class NoiseEstMADDevice(AbstractNoiseEstDevice):
     def __init__(self, template: NoiseEstMADDeviceTemplate, command_queue: AbstractCommandQueue,
                  channels: int, baselines: int,
                  allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
-        super().__init__(command_queue, allocator)
-        self.template = template
-        self.kernel = template.kernel
-        self.channels = channels
-        self.baselines = baselines
+        super().__init__(template, command_queue, channels, baselines, allocator)
         self.method = int(template.tuning.get("method", 0))
         if channels > self.MAX_TRANSPOSED_CHANNELS:
             self.method = 0
@@ -399,22 +374,19 @@ class NoiseEstMADDevice(AbstractNoiseEstDevice):
                 ],
             )
             return
-        self.command_queue.enqueue_kernel(
-            self.kernel,
-            [
-                deviations.buffer,
-                noise.buffer,
-                np.int32(self.channels),
-                np.int32(self.baselines),
-                np.int32(deviations.padded_shape[1]),
-            ],
+        self._launch(
+            deviations.buffer,
+            noise.buffer,
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(deviations.padded_shape[1]),
         )
 
     def parameters(self) -> Mapping[str, Any]:
-        return {"channels": self.channels, "baselines": self.baselines, "method": self.method}
+        return self._parameters(method=self.method)
 
 
-class NoiseEstMADTDeviceTemplate(AbstractNoiseEstDeviceTemplate):
+class NoiseEstMADTDeviceTemplate(_native_op.NativeTemplate, AbstractNoiseEstDeviceTemplate):
     """Median of non-zero absolute deviations on baseline-major data
     (reference rfi/device.py:475-549).
 
@@ -436,28 +408,18 @@ class NoiseEstMADTDeviceTemplate(AbstractNoiseEstDeviceTemplate):
     host_class = host.NoiseEstMADHost
     transposed = True
     MAX_CHANNELS_SUPPORTED = 256 * 1024
+    KERNEL = "ksp_madnz_t"
     TUNING_KEYS = ("wgsx",)
 
     def __init__(self, context: AbstractContext, max_channels: int,
                  tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
         if max_channels > self.MAX_CHANNELS_SUPPORTED:
             raise ValueError(f"max_channels exceeds {self.MAX_CHANNELS_SUPPORTED}")
-        self.context = context
         self.max_channels = max_channels
-        self.tuning = tune.fixed_geometry("NoiseEstMADTDeviceTemplate", tuning, self.TUNING_KEYS)
-        self.kernel = context.native_kernel("ksp_madnz_t")
-
-    @classmethod
-    def autotune(cls, context: AbstractContext, max_channels: int) -> Mapping[str, Any]:
-        """Nothing to search (reference rfi/device.py:523 times wgsx)."""
-        return {}
-
-    def instantiate(self, command_queue: AbstractCommandQueue, channels: int, baselines: int,
-                    allocator: Optional[AbstractAllocator] = None) -> "NoiseEstMADTDevice":  # fmt: skip
-        return NoiseEstMADTDevice(self, command_queue, channels, baselines, allocator)
+        self._setup(context, tuning)
 
 
-class NoiseEstMADTDevice(AbstractNoiseEstDevice):
+class NoiseEstMADTDevice(_native_op.NativeOperation, AbstractNoiseEstDevice):
     """Concrete :class:`NoiseEstMADTDeviceTemplate` (``ValueError`` if `channels` exceeds
     the template's ``max_channels``).
 
@@ -472,36 +434,27 @@ class NoiseEstMADTDevice(AbstractNoiseEstDevice):
     def __init__(self, template: NoiseEstMADTDeviceTemplate, command_queue: AbstractCommandQueue,
                  channels: int, baselines: int,
                  allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
-        super().__init__(command_queue, allocator)
+        super().__init__(template, command_queue, channels, baselines, allocator)
         if channels > template.max_channels:
             raise ValueError("channels exceeds max_channels")
-        self.template = template
-        self.kernel = template.kernel
-        self.channels = channels
-        self.baselines = baselines
         self.slots["noise"] = accel.IOSlot((baselines,), np.float32)
         self.slots["deviations"] = accel.IOSlot((baselines, channels), np.float32)
 
     def _run(self) -> None:
         deviations = self.buffer("deviations")
-        noise = self.buffer("noise")
-        self.command_queue.enqueue_kernel(
-            self.kernel,
-            [
-                deviations.buffer,
-                noise.buffer,
-                np.int32(self.channels),
-                np.int32(self.baselines),
-                np.int32(deviations.padded_shape[1]),
-            ],
+        self._launch(
+            deviations.buffer,
+            self.buffer("noise").buffer,
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(deviations.padded_shape[1]),
         )
 
     def parameters(self) -> Mapping[str, Any]:
-        return {
-            "max_channels": self.template.max_channels,
-            "baselines": self.baselines,
-            "channels": self.channels,
-        }
+        return self._parameters(max_channels=self.template.max_channels)
+
+
+NoiseEstMADTDeviceTemplate.operation_class = NoiseEstMADTDevice
 
 
 # -------------------------------------------------------------------------- threshold
@@ -518,41 +471,32 @@ class ThresholdHostFromDevice(host.AbstractThresholdHost):
 
     def __call__(self, deviations: np.ndarray, noise: np.ndarray) -> np.ndarray:
         channels, baselines = deviations.shape
-        transposed = self.template.transposed
-        if transposed:
-            deviations = deviations.T
         fn = self.template.instantiate(
             self.command_queue, channels, baselines, *self.args, **self.kwargs
         )
-        fn.ensure_all_bound()
-        fn.buffer("deviations").set(self.command_queue, deviations)
-        fn.buffer("noise").set(self.command_queue, noise)
-        fn()
-        flags = fn.buffer("flags").get(self.command_queue)
+        transposed = self.template.transposed
+        if transposed:
+            deviations = deviations.T
+        inputs = {"deviations": deviations, "noise": noise}
+        flags = _native_op.run_once(fn, self.command_queue, inputs, ["flags"])[0]
         return flags.T if transposed else flags
 
 
-class ThresholdSimpleDeviceTemplate(AbstractThresholdDeviceTemplate):
+class ThresholdSimpleDeviceTemplate(_native_op.NativeTemplate, AbstractThresholdDeviceTemplate):
     """Independent per-sample threshold, either memory order
     (reference rfi/device.py:654-720). The kernel's geometry is fixed: ``wgsx``/``wgsy`` of the
     reference are accepted in `tuning` without effect, any other key is a ``ValueError``
     (:func:`.tune.fixed_geometry`)."""
 
     host_class = host.ThresholdSimpleHost
+    KERNEL = "ksp_threshold_simple"
     TUNING_KEYS = ("wgsx", "wgsy")
 
     def __init__(self, context: AbstractContext, transposed: bool, flag_value: int = 1,
                  tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
-        self.context = context
         self.transposed = transposed
         self.flag_value = flag_value
-        self.tuning = tune.fixed_geometry("ThresholdSimpleDeviceTemplate", tuning, self.TUNING_KEYS)
-        self.kernel = context.native_kernel("ksp_threshold_simple")
-
-    @classmethod
-    def autotune(cls, context: AbstractContext) -> Mapping[str, Any]:
-        """Nothing to search (reference rfi/device.py:707 times wgsx/wgsy)."""
-        return {}
+        self._setup(context, tuning)
 
     def instantiate(self, command_queue: AbstractCommandQueue, channels: int, baselines: int,
                     n_sigma: float,
@@ -560,7 +504,7 @@ class ThresholdSimpleDeviceTemplate(AbstractThresholdDeviceTemplate):
         return ThresholdSimpleDevice(self, command_queue, channels, baselines, n_sigma, allocator)
 
 
-class ThresholdSimpleDevice(AbstractThresholdDevice):
+class ThresholdSimpleDevice(_native_op.NativeOperation, AbstractThresholdDevice):
     """Concrete :class:`ThresholdSimpleDeviceTemplate`.
 
     .. rubric:: Slots
@@ -573,14 +517,10 @@ class ThresholdSimpleDevice(AbstractThresholdDevice):
     def __init__(self, template: ThresholdSimpleDeviceTemplate,
                  command_queue: AbstractCommandQueue, channels: int, baselines: int,
                  n_sigma: float, allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
-        super().__init__(command_queue, allocator)
-        self.template = template
-        self.kernel = template.kernel
+        super().__init__(template, command_queue, channels, baselines, allocator)
         self.n_sigma = n_sigma
-        self.channels = channels
-        self.baselines = baselines
         self.transposed = template.transposed
-        shape = (baselines, channels) if self.transposed else (channels, baselines)
+        shape = self.layout(self.transposed)
         dims = (accel.Dimension(shape[0]), accel.Dimension(shape[1]))
         noise_dim = dims[0] if self.transposed else dims[1]
         self.slots["deviations"] = accel.IOSlot(dims, np.float32)
@@ -589,32 +529,27 @@ class ThresholdSimpleDevice(AbstractThresholdDevice):
 
     def _run(self) -> None:
         deviations = self.buffer("deviations")
-        self.command_queue.enqueue_kernel(
-            self.kernel,
-            [
-                deviations.buffer,
-                self.buffer("noise").buffer,
-                self.buffer("flags").buffer,
-                np.int32(deviations.shape[0]),
-                np.int32(deviations.shape[1]),
-                np.int32(deviations.padded_shape[1]),
-                np.float32(self.n_sigma),
-                np.int32(self.template.flag_value),
-                np.int32(self.transposed),
-            ],
+        self._launch(
+            deviations.buffer,
+            self.buffer("noise").buffer,
+            self.buffer("flags").buffer,
+            np.int32(deviations.shape[0]),
+            np.int32(deviations.shape[1]),
+            np.int32(deviations.padded_shape[1]),
+            np.float32(self.n_sigma),
+            np.int32(self.template.flag_value),
+            np.int32(self.transposed),
         )
 
     def parameters(self) -> Mapping[str, Any]:
-        return {
-            "n_sigma": self.n_sigma,
-            "flag_value": self.template.flag_value,
-            "transposed": self.transposed,
-            "channels": self.channels,
-            "baselines": self.baselines,
-        }
+        return self._parameters(
+            n_sigma=self.n_sigma,
+            flag_value=self.template.flag_value,
+            transposed=self.transposed,
+        )
 
 
-class ThresholdSumDeviceTemplate(AbstractThresholdDeviceTemplate):
+class ThresholdSumDeviceTemplate(_native_op.AutotunedTuning, AbstractThresholdDeviceTemplate):
     """SumThreshold on baseline-major data (reference rfi/device.py:812-907), or on
     channel-major data with ``transposed=False``.
 
@@ -659,17 +594,11 @@ class ThresholdSumDeviceTemplate(AbstractThresholdDeviceTemplate):
         self.flag_value = flag_value
         self.transposed = bool(transposed)
         if self.transposed:
-            self._tuning = dict(tuning) if tuning is not None else None  # resolved on first use
+            self._init_tuning(tuning, n_windows)
             self.kernel = context.native_kernel("ksp_threshold_sum")
         else:
-            self._tuning = dict(tuning) if tuning is not None else {}  # nothing to search
+            self._init_tuning({} if tuning is None else tuning)  # nothing to search
             self.kernel = context.native_kernel("ksp_threshold_sum_cm")
-
-    @property
-    def tuning(self) -> Mapping[str, Any]:
-        if self._tuning is None:
-            self._tuning = dict(self.autotune(self.context, self.n_windows))
-        return self._tuning
 
     @classmethod
     @tune.autotuner(test={"wgs": 256, "vt": 8})
@@ -706,7 +635,7 @@ class ThresholdSumDeviceTemplate(AbstractThresholdDeviceTemplate):
         )
 
 
-class ThresholdSumDevice(AbstractThresholdDevice):
+class ThresholdSumDevice(_native_op.NativeOperation, AbstractThresholdDevice):
     """Concrete :class:`ThresholdSumDeviceTemplate`.
 
     .. rubric:: Slots
@@ -724,11 +653,7 @@ class ThresholdSumDevice(AbstractThresholdDevice):
                  channels: int, baselines: int, n_sigma: float,
                  threshold_falloff: float = DEFAULT_THRESHOLD_FALLOFF,
                  allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
-        super().__init__(command_queue, allocator)
-        self.template = template
-        self.kernel = template.kernel
-        self.channels = channels
-        self.baselines = baselines
+        super().__init__(template, command_queue, channels, baselines, allocator)
         self.n_sigma = n_sigma
         self.threshold_falloff = threshold_falloff
         # python-float scales rounded to float32, as numpy does when the host class
@@ -737,73 +662,42 @@ class ThresholdSumDevice(AbstractThresholdDevice):
             [np.float32(pow(threshold_falloff, -i)) for i in range(template.n_windows)]
         ))
         self.transposed = template.transposed
-        if self.transposed:
-            # deviations and flags share the channel Dimension, hence the stride
-            dims = (baselines, accel.Dimension(channels))
-            self.slots["deviations"] = accel.IOSlot(dims, np.float32)
-            self.slots["noise"] = accel.IOSlot((baselines,), np.float32)
-            self.slots["flags"] = accel.IOSlot(dims, np.uint8)
-        else:
-            # as ThresholdSimpleDevice(transposed=False): one baseline Dimension throughout
-            dims = (channels, accel.Dimension(baselines))
-            self.slots["deviations"] = accel.IOSlot(dims, np.float32)
-            self.slots["noise"] = accel.IOSlot((dims[1],), np.float32)
-            self.slots["flags"] = accel.IOSlot(dims, np.uint8)
+        # deviations and flags share the Dimension of the fast axis, hence the stride; channel-
+        # major that axis is the baselines and noise shares it too, as in
+        # ThresholdSimpleDevice(transposed=False)
+        rows, columns = self.layout(self.transposed)
+        dims = (rows, accel.Dimension(columns))
+        noise_dim = baselines if self.transposed else dims[1]
+        self.slots["deviations"] = accel.IOSlot(dims, np.float32)
+        self.slots["noise"] = accel.IOSlot((noise_dim,), np.float32)
+        self.slots["flags"] = accel.IOSlot(dims, np.uint8)
 
     def _run(self) -> None:
         deviations = self.buffer("deviations")
-        if not self.transposed:
-            self.command_queue.enqueue_kernel(
-                self.kernel,
-                [
-                    deviations.buffer,
-                    self.buffer("noise").buffer,
-                    self.buffer("flags").buffer,
-                    np.int32(self.channels),
-                    np.int32(self.baselines),
-                    np.int32(deviations.padded_shape[1]),
-                    np.float32(self.n_sigma),
-                    self.scales,
-                    np.int32(self.template.n_windows),
-                    np.int32(self.template.flag_value),
-                ],
-            )
-            return
-        self.command_queue.enqueue_kernel(
-            self.kernel,
-            [
-                deviations.buffer,
-                self.buffer("noise").buffer,
-                self.buffer("flags").buffer,
-                np.int32(self.channels),
-                np.int32(self.baselines),
-                np.int32(deviations.padded_shape[1]),
-                np.float32(self.n_sigma),
-                self.scales,
-                np.int32(self.template.n_windows),
-                np.int32(self.template.flag_value),
-                np.int32(self.template.tuning.get("vt", 0)),
-            ],
-        )
+        args = [
+            deviations.buffer,
+            self.buffer("noise").buffer,
+            self.buffer("flags").buffer,
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(deviations.padded_shape[1]),
+            np.float32(self.n_sigma),
+            self.scales,
+            np.int32(self.template.n_windows),
+            np.int32(self.template.flag_value),
+        ]
+        if self.transposed:  # the channel-major launcher picks its own geometry
+            args.append(np.int32(self.template.tuning.get("vt", 0)))
+        self._launch(*args)
 
     def parameters(self) -> Mapping[str, Any]:
-        return {
-            "n_sigma": self.n_sigma,
-            "threshold_falloff": self.threshold_falloff,
-            "vt": self.template.tuning.get("vt", 0),
-            "flag_value": self.template.flag_value,
-            "transposed": self.transposed,
-            "channels": self.channels,
-            "baselines": self.baselines,
-        }
-
-
-def ctypes_float_array(values):
-    return (ctypes.c_float * len(values))(*[float(v) for v in values])
-
-
-def ctypes_double_array(values):
-    return (ctypes.c_double * len(values))(*[float(v) for v in values])
+        return self._parameters(
+            n_sigma=self.n_sigma,
+            threshold_falloff=self.threshold_falloff,
+            vt=self.template.tuning.get("vt", 0),
+            flag_value=self.template.flag_value,
+            transposed=self.transposed,
+        )
 
 
 # ---------------------------------------------------------------------------- flagger
@@ -866,8 +760,6 @@ class FlaggerDeviceTemplate:
 
     def fusable(self, channels: int) -> bool:
         """Can the fused kernel run this combination of stages at `channels`?"""
-        from .. import _lib
-
         bg, th = self.background, self.threshold
         if not isinstance(bg, BackgroundMedianFilterDeviceTemplate):
             return False
@@ -1184,8 +1076,6 @@ class FusedFlaggerDevice(accel.Operation):
         """Arm two events around the flagger kernel of the next call (excluding the
         zero-fill of `flags` that precedes it); returns (start, stop). After the queue
         has finished, ``stop.time_since(start)`` is that kernel's duration."""
-        from .. import _lib
-
         queue = self.command_queue
         start, stop = queue.create_event(), queue.create_event()
         _lib.call("ksp_flagger_fused_profile", ctypes.c_void_p(start.handle),
@@ -1220,25 +1110,18 @@ class FlaggerHostFromDevice(host.AbstractFlaggerHost):
         self.threshold_args = dict(threshold_args)
 
     def __call__(self, vis: np.ndarray, input_flags: Optional[np.ndarray] = None) -> np.ndarray:
-        if input_flags is not None and not self.template.background.use_flags:
-            raise TypeError("channel flags were provided but not included in the template")
-        if input_flags is None and self.template.background.use_flags:
-            raise TypeError("channel flags were expected but not provided")
+        _native_op.check_optional(input_flags, self.template.background.use_flags, "channel flags")
         channels, baselines = vis.shape
         fn = self.template.instantiate(
             self.command_queue, channels, baselines, self.background_args, self.noise_est_args,
             self.threshold_args,
         )  # fmt: skip
-        fn.ensure_all_bound()
-        fn.buffer("vis").set(self.command_queue, vis)
-        if input_flags is not None:
-            fn.buffer("input_flags").set(self.command_queue, input_flags)
-        fn()
-        return fn.buffer("flags").get(self.command_queue)
+        inputs = {"vis": vis, "input_flags": input_flags}
+        return _native_op.run_once(fn, self.command_queue, inputs, ["flags"])[0]
 
 
 # ------------------------------------------------------------------------ flag counts
-class FlagCountTemplate:
+class FlagCountTemplate(_native_op.NativeTemplate):
     """Count flagged samples per channel and per baseline, on the device (no reference
     counterpart: the reference's callers count on a host copy of the flags).
 
@@ -1265,28 +1148,18 @@ class FlagCountTemplate:
     """
 
     host_class = host.FlagCountHost
+    KERNEL = "ksp_flag_count"
 
     def __init__(self, context: AbstractContext, masks=(0xFF,), transposed: bool = False,
                  accumulate: bool = False,
                  tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
-        self.context = context
         self.masks = host.check_flag_masks(masks)
         self.transposed = bool(transposed)
         self.accumulate = bool(accumulate)
-        self.tuning = tune.fixed_geometry("FlagCountTemplate", tuning, ())
-        self.kernel = context.native_kernel("ksp_flag_count")
-
-    @classmethod
-    def autotune(cls, context: AbstractContext) -> Mapping[str, Any]:
-        """Nothing to search."""
-        return {}
-
-    def instantiate(self, command_queue: AbstractCommandQueue, channels: int, baselines: int,
-                    allocator: Optional[AbstractAllocator] = None) -> "FlagCount":  # fmt: skip
-        return FlagCount(self, command_queue, channels, baselines, allocator)
+        self._setup(context, tuning)
 
 
-class FlagCount(accel.Operation):
+class FlagCount(_native_op.NativeOperation):
     """Concrete :class:`FlagCountTemplate` (``ValueError`` if `channels` or `baselines` is
     below 1).
 
@@ -1300,16 +1173,11 @@ class FlagCount(accel.Operation):
     def __init__(self, template: FlagCountTemplate, command_queue: AbstractCommandQueue,
                  channels: int, baselines: int,
                  allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
-        super().__init__(command_queue, allocator)
-        if channels < 1 or baselines < 1:
-            raise ValueError("channels and baselines must be at least 1")
-        self.template = template
-        self.kernel = template.kernel
-        self.channels = channels
-        self.baselines = baselines
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        _check_shape(channels, baselines)
         self.transposed = template.transposed
         self.masks = (ctypes.c_uint8 * len(template.masks))(*template.masks)
-        shape = (baselines, channels) if self.transposed else (channels, baselines)
+        shape = self.layout(self.transposed)
         n_masks = len(template.masks)
         self.slots["flags"] = accel.IOSlot((shape[0], accel.Dimension(shape[1])), np.uint8)
         self.slots["channel_counts"] = accel.IOSlot(
@@ -1323,31 +1191,29 @@ class FlagCount(accel.Operation):
         names = ("baseline_counts", "channel_counts") if self.transposed else (
             "channel_counts", "baseline_counts")  # fmt: skip
         row_counts, col_counts = self.buffer(names[0]), self.buffer(names[1])
-        self.command_queue.enqueue_kernel(
-            self.kernel,
-            [
-                flags.buffer,
-                row_counts.buffer,
-                col_counts.buffer,
-                np.int32(flags.shape[0]),
-                np.int32(flags.shape[1]),
-                np.int32(flags.padded_shape[1]),
-                np.int32(row_counts.padded_shape[1]),
-                np.int32(col_counts.padded_shape[1]),
-                self.masks,
-                np.int32(len(self.masks)),
-                np.int32(self.template.accumulate),
-            ],
+        self._launch(
+            flags.buffer,
+            row_counts.buffer,
+            col_counts.buffer,
+            np.int32(flags.shape[0]),
+            np.int32(flags.shape[1]),
+            np.int32(flags.padded_shape[1]),
+            np.int32(row_counts.padded_shape[1]),
+            np.int32(col_counts.padded_shape[1]),
+            self.masks,
+            np.int32(len(self.masks)),
+            np.int32(self.template.accumulate),
         )
 
     def parameters(self) -> Mapping[str, Any]:
-        return {
-            "masks": self.template.masks,
-            "transposed": self.transposed,
-            "accumulate": self.template.accumulate,
-            "channels": self.channels,
-            "baselines": self.baselines,
-        }
+        return self._parameters(
+            masks=self.template.masks,
+            transposed=self.transposed,
+            accumulate=self.template.accumulate,
+        )
+
+
+FlagCountTemplate.operation_class = FlagCount
 
 
 class FlagCountHostFromDevice:
@@ -1363,21 +1229,18 @@ class FlagCountHostFromDevice:
 
     def __call__(self, flags: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         channels, baselines = flags.shape
+        fn = self.template.instantiate(self.command_queue, channels, baselines)
         if self.template.transposed:
             flags = flags.T
-        fn = self.template.instantiate(self.command_queue, channels, baselines)
-        fn.ensure_all_bound()
-        fn.buffer("flags").set(self.command_queue, flags)
-        fn()
-        return (fn.buffer("channel_counts").get(self.command_queue),
-                fn.buffer("baseline_counts").get(self.command_queue))  # fmt: skip
+        return tuple(_native_op.run_once(fn, self.command_queue, {"flags": flags},
+                                         ["channel_counts", "baseline_counts"]))  # fmt: skip
 
 
 # ------------------------------------------------------------ scale-invariant rank
 SIR_MAX_CHANNELS = 262144
 
 
-class ScaleInvariantRankTemplate:
+class ScaleInvariantRankTemplate(_native_op.NativeTemplate):
     """Scale-invariant rank (SIR) extension of flags along the channel axis, in place, on the
     device (no reference counterpart); see :class:`host.ScaleInvariantRankHost` for the rule,
     which the kernels match bit for bit.
@@ -1403,31 +1266,21 @@ class ScaleInvariantRankTemplate:
     """
 
     host_class = host.ScaleInvariantRankHost
+    KERNEL = "ksp_sir"
 
     def __init__(self, context: AbstractContext, eta: float, mask: int = 0xFF,
                  flag_value: int = 1, transposed: bool = False,
                  tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
         checked = host.ScaleInvariantRankHost(eta, mask, flag_value)
-        self.context = context
         self.eta = checked.eta
         self.eta_q = checked.eta_q
         self.mask = checked.mask
         self.flag_value = checked.flag_value
         self.transposed = bool(transposed)
-        self.tuning = tune.fixed_geometry("ScaleInvariantRankTemplate", tuning, ())
-        self.kernel = context.native_kernel("ksp_sir")
-
-    @classmethod
-    def autotune(cls, context: AbstractContext) -> Mapping[str, Any]:
-        """Nothing to search."""
-        return {}
-
-    def instantiate(self, command_queue: AbstractCommandQueue, channels: int, baselines: int,
-                    allocator: Optional[AbstractAllocator] = None) -> "ScaleInvariantRank":  # fmt: skip
-        return ScaleInvariantRank(self, command_queue, channels, baselines, allocator)
+        self._setup(context, tuning)
 
 
-class ScaleInvariantRank(accel.Operation):
+class ScaleInvariantRank(_native_op.NativeOperation):
     """Concrete :class:`ScaleInvariantRankTemplate` (``ValueError`` if `channels` or
     `baselines` is below 1, or `channels` above 262144).
 
@@ -1436,47 +1289,42 @@ class ScaleInvariantRank(accel.Operation):
     **flags** : channels x baselines (baselines x channels if transposed), uint8, in and out
     """
 
+    MAX_CHANNELS_SUPPORTED = SIR_MAX_CHANNELS
+
     def __init__(self, template: ScaleInvariantRankTemplate, command_queue: AbstractCommandQueue,
                  channels: int, baselines: int,
                  allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
-        super().__init__(command_queue, allocator)
-        if channels < 1 or baselines < 1:
-            raise ValueError("channels and baselines must be at least 1")
-        if channels > SIR_MAX_CHANNELS:
-            raise ValueError(f"at most {SIR_MAX_CHANNELS} channels")
-        self.template = template
-        self.kernel = template.kernel
-        self.channels = channels
-        self.baselines = baselines
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        _check_shape(channels, baselines)
+        if channels > self.MAX_CHANNELS_SUPPORTED:
+            raise ValueError(f"at most {self.MAX_CHANNELS_SUPPORTED} channels")
         self.transposed = template.transposed
-        shape = (baselines, channels) if self.transposed else (channels, baselines)
+        shape = self.layout(self.transposed)
         self.slots["flags"] = accel.IOSlot((shape[0], accel.Dimension(shape[1])), np.uint8)
 
     def _run(self) -> None:
         flags = self.buffer("flags")
-        self.command_queue.enqueue_kernel(
-            self.kernel,
-            [
-                flags.buffer,
-                np.int32(flags.shape[0]),
-                np.int32(flags.shape[1]),
-                np.int32(flags.padded_shape[1]),
-                np.int32(1 if self.transposed else 0),  # the axis the lines run along
-                np.int32(self.template.eta_q),
-                np.int32(self.template.mask),
-                np.int32(self.template.flag_value),
-            ],
+        self._launch(
+            flags.buffer,
+            np.int32(flags.shape[0]),
+            np.int32(flags.shape[1]),
+            np.int32(flags.padded_shape[1]),
+            np.int32(1 if self.transposed else 0),  # the axis the lines run along
+            np.int32(self.template.eta_q),
+            np.int32(self.template.mask),
+            np.int32(self.template.flag_value),
         )
 
     def parameters(self) -> Mapping[str, Any]:
-        return {
-            "eta_q": self.template.eta_q,
-            "mask": self.template.mask,
-            "flag_value": self.template.flag_value,
-            "transposed": self.transposed,
-            "channels": self.channels,
-            "baselines": self.baselines,
-        }
+        return self._parameters(
+            eta_q=self.template.eta_q,
+            mask=self.template.mask,
+            flag_value=self.template.flag_value,
+            transposed=self.transposed,
+        )
+
+
+ScaleInvariantRankTemplate.operation_class = ScaleInvariantRank
 
 
 class ScaleInvariantRankHostFromDevice:
@@ -1492,22 +1340,19 @@ class ScaleInvariantRankHostFromDevice:
     def __call__(self, flags: np.ndarray) -> np.ndarray:
         channels, baselines = flags.shape
         fn = self.template.instantiate(self.command_queue, channels, baselines)
-        fn.ensure_all_bound()
-        fn.buffer("flags").set(self.command_queue, flags.T if self.template.transposed else flags)
-        fn()
-        out = fn.buffer("flags").get(self.command_queue)
+        if self.template.transposed:
+            flags = flags.T
+        out = _native_op.run_once(fn, self.command_queue, {"flags": flags}, ["flags"])[0]
         return np.ascontiguousarray(out.T) if self.template.transposed else out
 
 
 # -------------------------------------------------------------------------- averaging
-def _check_average_shape(channels: int, baselines: int, channel_factor: int = 1) -> None:
-    if channels < 1 or baselines < 1:
-        raise ValueError("channels and baselines must be at least 1")
+def _check_average_shape(channels: int, channel_factor: int) -> None:
     if channel_factor < 1 or channels % channel_factor:
         raise ValueError("channel_factor must be at least 1 and divide channels")
 
 
-class AccumulateTemplate:
+class AccumulateTemplate(_native_op.NativeTemplate):
     """Add one dump of visibilities to device-resident accumulators, leaving flagged
     samples out (no reference counterpart: the reference's callers average in their own
     code). :class:`host.AveragerHost` defines the arithmetic of ``add``; the kernel matches
@@ -1533,27 +1378,17 @@ class AccumulateTemplate:
     """
 
     host_class = host.AveragerHost
+    KERNEL = "ksp_average_accumulate"
 
     def __init__(self, context: AbstractContext, use_weights: bool = True,
                  input_flags: BackgroundFlags = BackgroundFlags.NONE,
                  tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
-        self.context = context
         self.use_weights = bool(use_weights)
         self.input_flags = BackgroundFlags(input_flags)
-        self.tuning = tune.fixed_geometry("AccumulateTemplate", tuning, ())
-        self.kernel = context.native_kernel("ksp_average_accumulate")
-
-    @classmethod
-    def autotune(cls, context: AbstractContext) -> Mapping[str, Any]:
-        """Nothing to search."""
-        return {}
-
-    def instantiate(self, command_queue: AbstractCommandQueue, channels: int, baselines: int,
-                    allocator: Optional[AbstractAllocator] = None) -> "Accumulate":  # fmt: skip
-        return Accumulate(self, command_queue, channels, baselines, allocator)
+        self._setup(context, tuning)
 
 
-class Accumulate(accel.Operation):
+class Accumulate(_native_op.NativeOperation):
     """Concrete :class:`AccumulateTemplate` (``ValueError`` if `channels` or `baselines` is
     below 1).
 
@@ -1575,12 +1410,8 @@ class Accumulate(accel.Operation):
     def __init__(self, template: AccumulateTemplate, command_queue: AbstractCommandQueue,
                  channels: int, baselines: int,
                  allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
-        super().__init__(command_queue, allocator)
-        _check_average_shape(channels, baselines)
-        self.template = template
-        self.kernel = template.kernel
-        self.channels = channels
-        self.baselines = baselines
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        _check_shape(channels, baselines)
 
         def full(dtype) -> accel.IOSlot:
             return accel.IOSlot((channels, accel.Dimension(baselines)), dtype)
@@ -1603,39 +1434,36 @@ class Accumulate(accel.Operation):
         weights = self.buffer("weights") if self.template.use_weights else None
         in_flags = self.buffer("input_flags") if mode else None
         acc = [self.buffer(name) for name in ("acc_vis", "acc_weights", "acc_flags")]
-        self.command_queue.enqueue_kernel(
-            self.kernel,
-            [
-                vis.buffer,
-                flags.buffer,
-                weights.buffer if weights is not None else None,
-                in_flags.buffer if in_flags is not None else None,
-                np.int32(mode.value),
-                acc[0].buffer,
-                acc[1].buffer,
-                acc[2].buffer,
-                np.int32(self.channels),
-                np.int32(self.baselines),
-                np.int32(vis.padded_shape[1]),
-                np.int32(flags.padded_shape[1]),
-                np.int32(weights.padded_shape[1] if weights is not None else 0),
-                np.int32(in_flags.padded_shape[1] if mode == BackgroundFlags.FULL else 0),
-                np.int32(acc[0].padded_shape[1]),
-                np.int32(acc[1].padded_shape[1]),
-                np.int32(acc[2].padded_shape[1]),
-            ],
+        self._launch(
+            vis.buffer,
+            flags.buffer,
+            weights.buffer if weights is not None else None,
+            in_flags.buffer if in_flags is not None else None,
+            np.int32(mode.value),
+            acc[0].buffer,
+            acc[1].buffer,
+            acc[2].buffer,
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(vis.padded_shape[1]),
+            np.int32(flags.padded_shape[1]),
+            np.int32(weights.padded_shape[1] if weights is not None else 0),
+            np.int32(in_flags.padded_shape[1] if mode == BackgroundFlags.FULL else 0),
+            np.int32(acc[0].padded_shape[1]),
+            np.int32(acc[1].padded_shape[1]),
+            np.int32(acc[2].padded_shape[1]),
         )
 
     def parameters(self) -> Mapping[str, Any]:
-        return {
-            "use_weights": self.template.use_weights,
-            "input_flags": self.template.input_flags.name,
-            "channels": self.channels,
-            "baselines": self.baselines,
-        }
+        return self._parameters(
+            use_weights=self.template.use_weights, input_flags=self.template.input_flags.name
+        )
 
 
-class FinaliseTemplate:
+AccumulateTemplate.operation_class = Accumulate
+
+
+class FinaliseTemplate(_native_op.NativeTemplate):
     """Turn the accumulators of :class:`Accumulate` into averages: sum every
     `channel_factor` adjacent channels in order, divide by the summed weight, and report the
     flags of outputs whose contributions were all flagged (:meth:`host.AveragerHost.finalise`,
@@ -1656,28 +1484,18 @@ class FinaliseTemplate:
     """
 
     host_class = host.AveragerHost
+    KERNEL = "ksp_average_finalise"
 
     def __init__(self, context: AbstractContext, channel_factor: int = 1, clear: bool = True,
                  tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
         if channel_factor < 1:
             raise ValueError("channel_factor must be at least 1")
-        self.context = context
         self.channel_factor = int(channel_factor)
         self.clear = bool(clear)
-        self.tuning = tune.fixed_geometry("FinaliseTemplate", tuning, ())
-        self.kernel = context.native_kernel("ksp_average_finalise")
-
-    @classmethod
-    def autotune(cls, context: AbstractContext) -> Mapping[str, Any]:
-        """Nothing to search."""
-        return {}
-
-    def instantiate(self, command_queue: AbstractCommandQueue, channels: int, baselines: int,
-                    allocator: Optional[AbstractAllocator] = None) -> "Finalise":  # fmt: skip
-        return Finalise(self, command_queue, channels, baselines, allocator)
+        self._setup(context, tuning)
 
 
-class Finalise(accel.Operation):
+class Finalise(_native_op.NativeOperation):
     """Concrete :class:`FinaliseTemplate` (``ValueError`` if `channels` or `baselines` is
     below 1 or the template's `channel_factor` does not divide `channels`).
 
@@ -1694,12 +1512,9 @@ class Finalise(accel.Operation):
     def __init__(self, template: FinaliseTemplate, command_queue: AbstractCommandQueue,
                  channels: int, baselines: int,
                  allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
-        super().__init__(command_queue, allocator)
-        _check_average_shape(channels, baselines, template.channel_factor)
-        self.template = template
-        self.kernel = template.kernel
-        self.channels = channels
-        self.baselines = baselines
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        _check_shape(channels, baselines)
+        _check_average_shape(channels, template.channel_factor)
         out_channels = channels // template.channel_factor
         for prefix, rows in (("acc_", channels), ("", out_channels)):
             for name, dtype in (("vis", np.complex64), ("weights", np.float32), ("flags", np.uint8)):
@@ -1709,25 +1524,22 @@ class Finalise(accel.Operation):
     def _run(self) -> None:
         names = ("acc_vis", "acc_weights", "acc_flags", "vis", "weights", "flags")
         buffers = [self.buffer(name) for name in names]
-        self.command_queue.enqueue_kernel(
-            self.kernel,
-            [b.buffer for b in buffers]
-            + [
-                np.int32(self.channels),
-                np.int32(self.baselines),
-                np.int32(self.template.channel_factor),
-                np.int32(self.template.clear),
-            ]
-            + [np.int32(b.padded_shape[1]) for b in buffers],
+        self._launch(
+            *[b.buffer for b in buffers],
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(self.template.channel_factor),
+            np.int32(self.template.clear),
+            *[np.int32(b.padded_shape[1]) for b in buffers],
         )
 
     def parameters(self) -> Mapping[str, Any]:
-        return {
-            "channel_factor": self.template.channel_factor,
-            "clear": self.template.clear,
-            "channels": self.channels,
-            "baselines": self.baselines,
-        }
+        return self._parameters(
+            channel_factor=self.template.channel_factor, clear=self.template.clear
+        )
+
+
+FinaliseTemplate.operation_class = Finalise
 
 
 class AveragerHostFromDevice:
@@ -1755,25 +1567,15 @@ class AveragerHostFromDevice:
 
     def add(self, vis: np.ndarray, flags: np.ndarray, weights: Optional[np.ndarray] = None,
             input_flags: Optional[np.ndarray] = None) -> None:  # fmt: skip
-        if input_flags is not None and not self.input_flags:
-            raise TypeError("input_flags were provided but not included in the template")
-        if input_flags is None and self.input_flags:
-            raise TypeError("input_flags were expected but not provided")
+        _native_op.check_optional(input_flags, self.input_flags, "input_flags")
         if weights is not None and not self.use_weights:
             raise TypeError("weights were provided but not included in the template")
         fn = self._accumulate
-        fn.buffer("vis").set(self.command_queue, vis)
-        fn.buffer("flags").set(self.command_queue, flags)
-        if self.use_weights:
-            if weights is None:
-                weights = np.ones(fn.buffer("weights").shape, np.float32)
-            fn.buffer("weights").set(self.command_queue, weights)
-        if input_flags is not None:
-            fn.buffer("input_flags").set(self.command_queue, input_flags)
-        fn()
+        if self.use_weights and weights is None:
+            weights = np.ones(fn.buffer("weights").shape, np.float32)
+        inputs = {"vis": vis, "flags": flags, "weights": weights, "input_flags": input_flags}
+        _native_op.run_once(fn, self.command_queue, inputs, [])
 
     def finalise(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        fn = self._finalise
-        fn()
-        return tuple(fn.buffer(name).get(self.command_queue)
-                     for name in ("vis", "weights", "flags"))  # fmt: skip
+        return tuple(_native_op.run_once(self._finalise, self.command_queue, {},
+                                         ["vis", "weights", "flags"]))  # fmt: skip

@@ -18,7 +18,7 @@ from typing import Any, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .. import _lib, accel
+from .. import _lib, _native_op, accel
 from ..abc import AbstractCommandQueue, AbstractContext
 
 #: reference rfi/__init__.py
@@ -275,12 +275,9 @@ class SumThresholdFlagger(_Conditioned):
             return np.zeros(data.shape, np.bool_)
         template = self._device_template(amplitudes)
         op = template.instantiate(self._queue, n_time, n_freq, n_bl, batch=chunk_size or None)
-        op.ensure_all_bound()
-        op.buffer("data").set(self._queue, np.ascontiguousarray(data))
-        op.buffer("input_flags").set(self._queue, np.ascontiguousarray(flags != 0).view(np.uint8))
-        op()
-        out = op.buffer("flags").get(self._queue)
-        return out.view(np.bool_)
+        inputs = {"data": np.ascontiguousarray(data),
+                  "input_flags": np.ascontiguousarray(flags != 0).view(np.uint8)}  # fmt: skip
+        return _native_op.run_once(op, self._queue, inputs, ["flags"])[0].view(np.bool_)
 
 
 def _filter_radius(sigma: float, passes: int) -> int:
@@ -483,9 +480,7 @@ def masked_gaussian_filter(data, flags, sigma, out, passes=4, *, context=None):
     context, queue = _filter_queue(context)
     template = MaskedGaussianFilterTemplate(context, data_dtype, passes)
     op = template.instantiate(queue, data.shape, sigma)
-    op.ensure_all_bound()
-    op.buffer("data").set(queue, np.ascontiguousarray(data))
-    op.buffer("flags").set(queue, np.ascontiguousarray(flags != 0).view(np.uint8))
-    op()
-    out[...] = op.buffer("out").get(queue)
+    inputs = {"data": np.ascontiguousarray(data),
+              "flags": np.ascontiguousarray(flags != 0).view(np.uint8)}  # fmt: skip
+    out[...] = _native_op.run_once(op, queue, inputs, ["out"])[0]
     return None

@@ -4,11 +4,11 @@ from typing import Any, Mapping, Optional, Tuple
 
 import numpy as np
 
-from . import accel, tune
+from . import _native_op, accel
 from .abc import AbstractCommandQueue, AbstractContext
 
 
-class TransposeTemplate:
+class TransposeTemplate(_native_op.NativeTemplate):
     """Transpose a 2-D array of any 1/2/4/8/16-byte element type.
 
     Parameters
@@ -26,22 +26,16 @@ class TransposeTemplate:
         (:func:`.tune.fixed_geometry`).
     """
 
+    KERNEL = "ksp_transpose"
     TUNING_KEYS = ("block", "vtx", "vty")
 
     def __init__(self, context: AbstractContext, dtype, ctype: str = "",
                  tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
-        self.context = context
         self.dtype = np.dtype(dtype)
         self.ctype = ctype
         if self.dtype.itemsize not in (1, 2, 4, 8, 16):
             raise ValueError(f"unsupported element size {self.dtype.itemsize}")
-        self.tuning = tune.fixed_geometry("TransposeTemplate", tuning, self.TUNING_KEYS)
-        self.kernel = context.native_kernel("ksp_transpose")
-
-    @classmethod
-    def autotune(cls, context: AbstractContext, dtype, ctype: str) -> Mapping[str, Any]:
-        """Nothing to search (reference transpose.py:87-108 times block/vtx/vty)."""
-        return {}
+        self._setup(context, tuning)
 
     def instantiate(self, command_queue: AbstractCommandQueue, shape: Tuple[int, int],
                     allocator: Optional[accel.AbstractAllocator] = None) -> "Transpose":  # fmt: skip
