@@ -147,6 +147,16 @@ int ksp_background_median_filter(int device, void *stream, const void *in, float
                                  int flags_stride, int width, int is_amplitude, int flags_mode,
                                  int csplit);
 
+/* How ksp_background_median_filter cuts the band for widths 3 .. 31 (no reference
+ * counterpart: the tests use it to know which segment computed a channel). A wavefront
+ * walks one segment of *seg_len channels for 64 adjacent baselines; segment i covers channels
+ * [i * seg_len, min(channels, (i + 1) * seg_len)), and there are *n_segs of them. It is the
+ * function the launcher itself calls. An empty band (channels or baselines 0) gives 0 and 0.
+ * Host arithmetic only, no device call. Any other width is an error: the wide-window kernel
+ * (33 .. 255) has a geometry of its own. */
+int ksp_background_median_filter_geometry(int channels, int baselines, int width, int csplit,
+                                          int *seg_len, int *n_segs);
+
 /* madnz_t (reference: rfi/madnz_t.mako:72-87; launch rfi/device.py:594-607).
  * in: [B][stride] float32; noise[b] = float32(1.4826 * median(|x| : x != 0)).
  * channels 1..262144; more is rejected before any device call. */

@@ -114,6 +114,9 @@ SIGNATURES = {
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
         c_int, c_int,
     ],
+    "ksp_background_median_filter_geometry": [
+        c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)
+    ],
     "ksp_madnz_t": [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int],
     "ksp_madnz": [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int],
     "ksp_threshold_simple": [

@@ -192,24 +192,51 @@ __global__ __launch_bounds__(256) void background_kernel(
     }
 }
 
+// The channel segments of background_kernel<width> (widths 3 .. 31): csplit = number of
+// segments a baseline is cut into (each segment re-reads width - 1 channels of halo); 0: aim
+// for >= 8192 wavefronts. Segments are at least 4 * width channels long either way, and
+// never longer than the band. channels and baselines are positive.
+static void background_geometry(int channels, int baselines, int width, int csplit, int *seg_len,
+                                int *n_segs)
+{
+    const int wave_cols = ksp_divup(baselines, 64);
+    const int want_segs = csplit > 0 ? csplit : ksp_divup(8192, wave_cols);
+    int len = ksp_divup(channels, want_segs);
+    if (len < 4 * width) len = 4 * width;
+    if (len > channels) len = channels;
+    *seg_len = len;
+    *n_segs = ksp_divup(channels, len);
+}
+
 template <int WIDTH>
 static int launch_background(hipStream_t s, const void *in, float *out, const uint8_t *flags,
                              int channels, int baselines, int stride, int flags_stride,
                              int is_amplitude, int flags_mode, int csplit)
 {
-    const int wave_cols = ksp_divup(baselines, 64);
-    // csplit = number of channel segments a baseline is cut into (each segment re-reads
-    // WIDTH - 1 channels of halo); 0: aim for >= 8192 wavefronts. Segments are at least
-    // 4 * WIDTH channels long either way.
-    int want_segs = csplit > 0 ? csplit : ksp_divup(8192, wave_cols);
-    int seg_len = ksp_divup(channels, want_segs);
-    if (seg_len < 4 * WIDTH) seg_len = 4 * WIDTH;
-    if (seg_len > channels) seg_len = channels;
-    const int segs = ksp_divup(channels, seg_len);
-    dim3 grid(wave_cols, ksp_divup(segs, 4));
+    int seg_len, segs;
+    background_geometry(channels, baselines, WIDTH, csplit, &seg_len, &segs);
+    dim3 grid(ksp_divup(baselines, 64), ksp_divup(segs, 4));
     hipLaunchKernelGGL(background_kernel<WIDTH>, grid, dim3(256), 0, s, in, out, flags, channels,
                        baselines, stride, flags_stride, seg_len, is_amplitude, flags_mode);
     KSP_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ksp_background_median_filter_geometry(int channels, int baselines, int width,
+                                                     int csplit, int *seg_len, int *n_segs)
+{
+    KSP_REQUIRE(seg_len != nullptr && n_segs != nullptr, "NULL result pointer");
+    KSP_REQUIRE(channels >= 0 && baselines >= 0, "bad shape");
+    if (width < 3 || width > 31 || !(width & 1)) {
+        ksp_set_error("ksp_background_median_filter_geometry: width %d is not odd in 3..31 "
+                      "(wider windows run the wide-window kernel, which has its own geometry)",
+                      width);
+        return (int)hipErrorInvalidValue;
+    }
+    KSP_REQUIRE(csplit >= 0, "csplit is negative");
+    *seg_len = *n_segs = 0;  // an empty band launches nothing
+    if (channels > 0 && baselines > 0)
+        background_geometry(channels, baselines, width, csplit, seg_len, n_segs);
     return 0;
 }
 

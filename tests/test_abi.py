@@ -59,6 +59,12 @@ def test_abi_version_and_no_device_calls(lib):
     assert before in (-1, 0, 1) and lib.ksp_flagger_fused_ring_mode(7) == 1  # (7: query only)
     assert lib.ksp_flagger_fused_ring_mode(before) == 1
     assert lib.ksp_flagger_fused_supported(4096, 12, 4) == 0
+    seg_len, n_segs = ctypes.c_int(-1), ctypes.c_int(-1)
+    out = (ctypes.byref(seg_len), ctypes.byref(n_segs))
+    assert lib.ksp_background_median_filter_geometry(4096, 8192, 13, 0, *out) == 0
+    assert (seg_len.value, n_segs.value) == (64, 64)  # the 64 segments of test_config3_shape
+    assert lib.ksp_background_median_filter_geometry(417, 313, 13, 4, *out) == 0
+    assert (seg_len.value, n_segs.value) == (105, 4)
 
 
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
@@ -80,6 +86,10 @@ def test_argument_validation_without_gpu(lib):
                                ctypes.c_void_p(8), 16, 4, 16, 11.0,
                                (ctypes.c_float * 9)(), 9, 1, 0)  # fmt: skip
     assert rc != 0 and "n_windows" in _lib.last_error()
+    seg_len, n_segs = ctypes.c_int(), ctypes.c_int()
+    rc = lib.ksp_background_median_filter_geometry(4096, 64, 33, 0, ctypes.byref(seg_len),
+                                                   ctypes.byref(n_segs))  # fmt: skip
+    assert rc != 0 and "width 33" in _lib.last_error()
 
 
 def test_fused_ring_mode_and_path_names(lib):

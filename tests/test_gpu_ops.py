@@ -218,7 +218,8 @@ class TestBackground:
 
     @pytest.mark.parametrize("width", list(range(3, 32, 2)))
     def test_every_width(self, width, context, command_queue, oracle):
-        """Every compiled window width (odd, 3 to 31), per-sample flags."""
+        """Every compiled window width (odd, 3 to 31), per-sample flags: the sorted-window
+        median at every width (test_gpu_background_segments.py runs the same without flags)."""
         from katsdpsigproc_amd.rfi import device
 
         vis_big, flags_big = inputs.background_case()
@@ -254,7 +255,10 @@ class TestBackground:
 
     @pytest.mark.parametrize("csplit", [0, 1, 3, 8, 64, 1000])
     def test_every_channel_split(self, csplit, context, command_queue, oracle):
-        """The tunable only changes who computes what: any split gives the same bits."""
+        """The tunable only changes who computes what: any split gives the same bits. With
+        per-sample flags every segment takes the sorted-window median, so this covers that
+        median alone; test_every_channel_split_no_flags (test_gpu_background_segments.py) runs
+        the same splits where interior segments take the merging median."""
         from katsdpsigproc_amd.rfi import device
 
         vis_big, flags_big = inputs.background_case()
