@@ -447,6 +447,37 @@ int ksp_average_finalise(int device, void *stream, void *acc_vis, float *acc_wei
 int ksp_sir(int device, void *stream, uint8_t *flags, int rows, int cols, int stride, int axis,
             int eta_q, int mask, int flag_value);
 
+/* prepare: a correlator's integer dump as the inputs of the flagging chain, in one launch (no
+ * reference counterpart; bit for bit what rfi/host.py PrepareHost computes; every float step
+ * is one float32 operation, rounded once).
+ * vis_in: [channels][vis_in_stride] pairs (re, im) of int32, of which in_baselines are data.
+ * source: int32 [baselines]; auto_source: int32 [baselines][2], contiguous. vis: complex64,
+ * input_flags: uint8, weights: float32, each [channels][its stride], baselines contiguous.
+ * Strides are in elements of their array (pairs for vis_in, complex numbers for vis).
+ * Per channel c and output baseline j, with s = source[j]:
+ *   lost = s outside 0 .. in_baselines - 1, or vis_in[c][s].re == -2^31 (a sample that was
+ *          never received; vis_in[c][s].im == -2^31 alone is data);
+ *   vis = lost ? (0, 0) : (float(re) * scale, float(im) * scale);
+ *   input_flags = (channel_flags ? channel_flags[c] : 0) | (lost ? lost_flag : 0);
+ *   power(k) = k inside 0 .. in_baselines - 1 and vis_in[c][k].re != -2^31
+ *              ? float(vis_in[c][k].re) * scale : 0;
+ *   pa = power(auto_source[j][0]), pb = power(auto_source[j][1]), d = pa * pb;
+ *   weights = pa > 0 && pb > 0 && d > 0 ? weight_scale / d : 0 (correctly rounded).
+ * Any int32 is allowed in source and auto_source: an index outside the range is never used
+ * to form an address. channel_flags (uint8 [channels]) may be NULL; auto_source and weights
+ * are both NULL (no weights; weights_stride and weight_scale are then ignored) or both given.
+ * scale and weight_scale are finite and positive, lost_flag is 1 .. 255. Elements between
+ * baselines and a stride are never written, elements between in_baselines and vis_in_stride
+ * never read. 16-byte stores need vis, input_flags, weights, source and auto_source and every
+ * row start to be multiples of 16 bytes and vis_in a multiple of 8; anything else takes a
+ * slower element-wise path with the same result. Every argument is checked before any device
+ * call. */
+int ksp_prepare(int device, void *stream, const int32_t *vis_in, const int32_t *source,
+                const int32_t *auto_source, const uint8_t *channel_flags, void *vis,
+                uint8_t *input_flags, float *weights, int channels, int in_baselines,
+                int baselines, int vis_in_stride, int vis_stride, int input_flags_stride,
+                int weights_stride, float scale, float weight_scale, int lost_flag);
+
 /* ---- masked_gaussian_filter (reference rfi/twodflag.py:254-400) ----
  * Images [images][rows][cols] of float32 (itemsize 4) or float64 (itemsize 8); data, flags
  * (uint8, non-zero = flagged) and out share image_stride and row_stride, in elements

@@ -1,7 +1,7 @@
 """What the template/operation pairs over an ahead-of-time compiled launcher have in common,
 written down once. Private: the public classes live in the modules that use these
-(``rfi.device``, ``percentile``, ``maskedsum``, ``transpose``); DESIGN.md, "Adding an
-operation", says how the pieces go together.
+(``rfi.device``, ``rfi.ingest``, ``percentile``, ``maskedsum``, ``transpose``); DESIGN.md,
+"Adding an operation", says how the pieces go together.
 """
 
 from typing import Any, List, Mapping, Optional, Sequence, Tuple

@@ -423,6 +423,118 @@ class AveragerHost:
         return vis, w, out_flags
 
 
+def _check_positive_float32(name: str, value) -> np.float32:
+    """`value` as a finite, positive float32 (``ValueError`` otherwise)."""
+    with np.errstate(all="ignore"):
+        value32 = np.float32(value)
+    if not (np.isfinite(value32) and value32 > 0):
+        raise ValueError(f"{name} {value!r} is not a finite positive float32")
+    return value32
+
+
+def _check_array(name: str, value, dtype, shape_text: str, ok) -> np.ndarray:
+    """`value` as an array, ``ValueError`` naming it unless it has `dtype` and `ok(shape)`."""
+    value = np.asarray(value)
+    if value.dtype != np.dtype(dtype) or not ok(value.shape):
+        raise ValueError(f"{name} must be {np.dtype(dtype).name} of shape {shape_text}, not "
+                         f"{value.dtype.name} {value.shape}")  # fmt: skip
+    return value
+
+
+class PrepareHost:
+    """A correlator's integer dump as the inputs of the flagging chain: ``vis`` (complex64),
+    ``input_flags`` (uint8, the FULL mask of the flagger and of :class:`AveragerHost`) and,
+    optionally, ``weights`` (float32), all channels x baselines. No reference counterpart;
+    this class is the definition that the device operation (:class:`.ingest.PrepareTemplate`)
+    matches bit for bit.
+
+    `vis_in` holds saturating int32 accumulations as (re, im) pairs in the correlator's own
+    baseline order; ``source[j]`` names the input baseline that feeds output baseline ``j`` (a
+    gather: repeats are allowed). A sample whose real part is ``-2**31`` was never received
+    (a saturated accumulator clamps to ``+-(2**31 - 1)`` and never gives that value; an
+    imaginary part of ``-2**31`` alone is data). Per channel ``c`` and output baseline ``j``::
+
+        s    = source[j];  valid = 0 <= s < in_baselines
+        lost = not valid or vis_in[c, s].re == -2**31
+        vis  = lost ? 0 : (float32(re) * scale, float32(im) * scale)
+        input_flags = channel_flags[c] | (lost ? lost_flag : 0)
+
+    and, with `auto_source` (the input baselines of the autocorrelations of the two inputs of
+    every output baseline)::
+
+        power(k) = valid k and vis_in[c, k].re != -2**31 ? float32(vis_in[c, k].re) * scale : 0
+        pa, pb = power(auto_source[j, 0]), power(auto_source[j, 1]);  d = pa * pb
+        weights = (pa > 0 and pb > 0 and d > 0) ? weight_scale / d : 0
+
+    Every float step is one float32 operation, rounded once (the conversion from int32
+    rounds to nearest even). A weight does not depend on whether its own sample is lost. Any
+    int32 is allowed in `source` and `auto_source`; no NaN can arise.
+
+    Parameters
+    ----------
+    scale, weight_scale
+        Taken as ``np.float32``; finite and positive (``ValueError``)
+    lost_flag
+        Bits set in ``input_flags`` of a lost sample, 1..255 (:func:`check_flag_byte`)
+    """
+
+    LOST = np.int32(-(2**31))
+
+    def __init__(self, scale: float = 1.0, lost_flag: int = 8, weight_scale: float = 1.0) -> None:
+        self.scale = _check_positive_float32("scale", scale)
+        self.lost_flag = check_flag_byte("lost_flag", lost_flag)
+        self.weight_scale = _check_positive_float32("weight_scale", weight_scale)
+
+    def _power(self, vis_in: np.ndarray, index: np.ndarray) -> np.ndarray:
+        valid = (index >= 0) & (index < vis_in.shape[1])
+        re = vis_in[:, np.where(valid, index, 0), 0]
+        good = valid[np.newaxis, :] & (re != self.LOST)
+        return np.where(good, re.astype(np.float32) * self.scale, np.float32(0))
+
+    def __call__(self, vis_in: np.ndarray, source: np.ndarray,
+                 channel_flags: Optional[np.ndarray] = None,
+                 auto_source: Optional[np.ndarray] = None):  # fmt: skip
+        """``(vis, input_flags, weights)`` for int32 `vis_in` (channels, in_baselines, 2),
+        int32 `source` (baselines,), optional uint8 `channel_flags` (channels,) and optional
+        int32 `auto_source` (baselines, 2); ``weights`` is ``None`` without `auto_source`.
+        ``ValueError``, naming the argument, for a wrong dtype, rank or shape."""
+        vis_in = _check_array("vis_in", vis_in, np.int32, "(channels, in_baselines, 2)",
+                              lambda s: len(s) == 3 and s[0] >= 1 and s[1] >= 1 and s[2] == 2)  # fmt: skip
+        channels = vis_in.shape[0]
+        source = _check_array("source", source, np.int32, "(baselines,)",
+                              lambda s: len(s) == 1 and s[0] >= 1)  # fmt: skip
+        baselines = source.shape[0]
+        if channel_flags is not None:
+            channel_flags = _check_array("channel_flags", channel_flags, np.uint8, "(channels,)",
+                                         lambda s: s == (channels,))  # fmt: skip
+        if auto_source is not None:
+            auto_source = _check_array("auto_source", auto_source, np.int32, "(baselines, 2)",
+                                       lambda s: s == (baselines, 2))  # fmt: skip
+        valid = (source >= 0) & (source < vis_in.shape[1])
+        picked = vis_in[:, np.where(valid, source, 0)]
+        lost = ~valid[np.newaxis, :] | (picked[..., 0] == self.LOST)
+        vis = np.zeros((channels, baselines), np.complex64)
+        with np.errstate(all="ignore"):
+            scaled = picked.astype(np.float32) * self.scale
+        vis.real[...] = np.where(lost, np.float32(0), scaled[..., 0])
+        vis.imag[...] = np.where(lost, np.float32(0), scaled[..., 1])
+        input_flags = np.where(lost, np.uint8(self.lost_flag), np.uint8(0))
+        if channel_flags is not None:
+            input_flags = input_flags | channel_flags[:, np.newaxis]
+        weights = None
+        if auto_source is not None:
+            with np.errstate(all="ignore"):
+                pa = self._power(vis_in, auto_source[:, 0])
+                pb = self._power(vis_in, auto_source[:, 1])
+                d = pa * pb
+                ok = (pa > 0) & (pb > 0) & (d > 0)
+                # (the divisor of a sample that gets no weight is 1, not d: no 1 / 0)
+                weights = np.where(ok, self.weight_scale / np.where(ok, d, np.float32(1)),
+                                   np.float32(0))  # fmt: skip
+            weights = np.ascontiguousarray(weights)  # (the gathers above come column-major)
+        return vis, input_flags, weights
+
+
 class FlaggerHost(AbstractFlaggerHost):
     """background -> noise estimate -> threshold (reference rfi/host.py:257-273)."""
 

@@ -1,0 +1,174 @@
+"""The step in front of the flagging chain: a correlator's integer dump, as it arrives, to the
+``vis``, ``input_flags`` and ``weights`` that :mod:`.device` takes as inputs, in one kernel
+launch (no reference counterpart). :class:`.host.PrepareHost` is the definition; the kernel
+matches it bit for bit. The classes follow DESIGN.md, "Adding an operation".
+"""
+
+from typing import Any, Mapping, Optional, Tuple
+
+import numpy as np
+
+from .. import _native_op, accel
+from ..abc import AbstractCommandQueue, AbstractContext
+from ..accel import AbstractAllocator
+from . import host
+
+
+class PrepareTemplate(_native_op.NativeTemplate):
+    """Gather the baselines the pipeline keeps from a dump of saturating int32 (re, im)
+    accumulations, scale them to complex64, mark the samples the correlator never received
+    and, optionally, derive weights from the autocorrelations; see :class:`host.PrepareHost`
+    for every step.
+
+    The three outputs are the inputs of the rest of the chain: ``vis`` and ``input_flags`` are
+    the slots of those names of the fused flagger (``use_flags=BackgroundFlags.FULL``) and of
+    :class:`.device.Accumulate` (``input_flags=BackgroundFlags.FULL``), ``weights`` is
+    :class:`.device.Accumulate`'s; share them through the ``compounds`` of an
+    :class:`.accel.OperationSequence`.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    scale, lost_flag, weight_scale
+        As for :class:`host.PrepareHost` (same errors)
+    channel_flags
+        ``True``: there is a `channel_flags` slot, one byte per channel that is ORed into
+        every sample of its channel
+    weights
+        ``True``: there are an `auto_source` and a `weights` slot
+    tuning
+        The kernel picks its launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.PrepareHost
+    KERNEL = "ksp_prepare"
+
+    def __init__(self, context: AbstractContext, scale: float = 1.0, lost_flag: int = 8,
+                 channel_flags: bool = False, weights: bool = False, weight_scale: float = 1.0,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        checked = host.PrepareHost(scale, lost_flag, weight_scale)
+        self.scale = checked.scale
+        self.lost_flag = checked.lost_flag
+        self.weight_scale = checked.weight_scale
+        self.channel_flags = bool(channel_flags)
+        self.weights = bool(weights)
+        self._setup(context, tuning)
+
+
+class Prepare(_native_op.NativeOperation):
+    """Concrete :class:`PrepareTemplate` (``ValueError`` if `channels`, `baselines` or
+    `in_baselines` is below 1). `in_baselines`, the number of baselines of the dump, defaults
+    to `baselines`, the number the pipeline keeps.
+
+    .. rubric:: Slots
+
+    **vis_in** : channels x in_baselines x 2, int32, (re, im)
+    **source** : baselines, int32: the input baseline of every output baseline
+    **channel_flags** : channels, uint8 (only with ``channel_flags``)
+    **auto_source** : baselines x 2, int32: the input baselines of the two autocorrelations
+    of every output baseline (only with ``weights``)
+    **vis** : channels x baselines, complex64
+    **input_flags** : channels x baselines, uint8
+    **weights** : channels x baselines, float32 (only with ``weights``)
+
+    Every padded dimension is an object of its own, so each output can be compounded with
+    its consumer's slot and take its padding.
+    """
+
+    def __init__(self, template: PrepareTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int, in_baselines: Optional[int] = None,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        if in_baselines is None:
+            in_baselines = baselines
+        if channels < 1 or baselines < 1 or in_baselines < 1:
+            raise ValueError("channels, baselines and in_baselines must be at least 1")
+        self.in_baselines = in_baselines
+
+        def pair() -> accel.Dimension:
+            return accel.Dimension(2, exact=True)
+
+        def full(dtype) -> accel.IOSlot:
+            return accel.IOSlot((channels, accel.Dimension(baselines)), dtype)
+
+        self.slots["vis_in"] = accel.IOSlot(
+            (channels, accel.Dimension(in_baselines), pair()), np.int32)  # fmt: skip
+        self.slots["source"] = accel.IOSlot((accel.Dimension(baselines),), np.int32)
+        if template.channel_flags:
+            self.slots["channel_flags"] = accel.IOSlot((accel.Dimension(channels),), np.uint8)
+        if template.weights:
+            self.slots["auto_source"] = accel.IOSlot(
+                (accel.Dimension(baselines), pair()), np.int32)  # fmt: skip
+        self.slots["vis"] = full(np.complex64)
+        self.slots["input_flags"] = full(np.uint8)
+        if template.weights:
+            self.slots["weights"] = full(np.float32)
+
+    def _run(self) -> None:
+        template = self.template
+        vis_in, source = self.buffer("vis_in"), self.buffer("source")
+        channel_flags = self.buffer("channel_flags") if template.channel_flags else None
+        auto_source = self.buffer("auto_source") if template.weights else None
+        vis, input_flags = self.buffer("vis"), self.buffer("input_flags")
+        weights = self.buffer("weights") if template.weights else None
+        self._launch(
+            vis_in.buffer,
+            source.buffer,
+            auto_source.buffer if auto_source is not None else None,
+            channel_flags.buffer if channel_flags is not None else None,
+            vis.buffer,
+            input_flags.buffer,
+            weights.buffer if weights is not None else None,
+            np.int32(self.channels),
+            np.int32(self.in_baselines),
+            np.int32(self.baselines),
+            np.int32(vis_in.padded_shape[1]),
+            np.int32(vis.padded_shape[1]),
+            np.int32(input_flags.padded_shape[1]),
+            np.int32(weights.padded_shape[1] if weights is not None else 0),
+            np.float32(template.scale),
+            np.float32(template.weight_scale),
+            np.int32(template.lost_flag),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        template = self.template
+        return self._parameters(
+            scale=float(template.scale),
+            lost_flag=template.lost_flag,
+            channel_flags=template.channel_flags,
+            weights=template.weights,
+            weight_scale=float(template.weight_scale),
+            in_baselines=self.in_baselines,
+        )
+
+
+PrepareTemplate.operation_class = Prepare
+
+
+class PrepareHostFromDevice:
+    """Make a :class:`PrepareTemplate` callable like :class:`host.PrepareHost`:
+    ``(vis_in, source, channel_flags=None, auto_source=None)`` in, ``(vis, input_flags,
+    weights or None)`` out; allocates on every call. ``TypeError`` unless `channel_flags` and
+    `auto_source` are given exactly when the template has them."""
+
+    def __init__(self, template: PrepareTemplate, command_queue: AbstractCommandQueue) -> None:
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, vis_in: np.ndarray, source: np.ndarray,
+                 channel_flags: Optional[np.ndarray] = None,
+                 auto_source: Optional[np.ndarray] = None
+                 ) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:  # fmt: skip
+        template = self.template
+        _native_op.check_optional(channel_flags, template.channel_flags, "channel_flags")
+        _native_op.check_optional(auto_source, template.weights, "auto_source")
+        channels, in_baselines = vis_in.shape[:2]
+        fn = template.instantiate(self.command_queue, channels, source.shape[0], in_baselines)
+        inputs = {"vis_in": vis_in, "source": source, "channel_flags": channel_flags,
+                  "auto_source": auto_source}  # fmt: skip
+        outputs = ["vis", "input_flags"] + (["weights"] if template.weights else [])
+        out = _native_op.run_once(fn, self.command_queue, inputs, outputs)
+        return out[0], out[1], (out[2] if template.weights else None)
