@@ -478,6 +478,27 @@ int ksp_prepare(int device, void *stream, const int32_t *vis_in, const int32_t *
                 int baselines, int vis_in_stride, int vis_stride, int input_flags_stride,
                 int weights_stride, float scale, float weight_scale, int lost_flag);
 
+/* compress_weights: float32 weights as one byte per sample and one float32 per channel, in
+ * one launch (no reference counterpart; bit for bit what rfi/host.py CompressWeightsHost
+ * computes; every float step is one float32 operation, rounded once).
+ * weights: float32 [channels][weights_stride]; weights8: uint8 [channels][weights8_stride];
+ * baselines contiguous, strides in elements; weights_channel: float32 [channels].
+ * Per channel c, with ok(w) = w > 0 and w < +inf:
+ *   m  = max over b of (ok(weights[c][b]) ? weights[c][b] : +0);
+ *   weights_channel[c] = wc = m / 255 (correctly rounded);
+ *   t = weights[c][b] / wc (correctly rounded; IEEE when wc == 0);
+ *   weights8[c][b] = !(weights[c][b] > 0) ? 0 : t >= 255 ? 255 : max(1, rint(t)), ties to even.
+ * A byte is 0 exactly where the weight is zero, negative or NaN; +inf takes no part in the
+ * maximum and becomes 255; with wc == 0 every positive weight becomes 255. Elements between
+ * baselines and weights_stride are never read, elements between baselines and weights8_stride
+ * never written. Rows of up to 32768 baselines are read once, longer rows twice. 16-byte loads
+ * need weights and every row start of it to be multiples of 16 bytes, 16-byte stores the same
+ * of weights8; anything else takes a slower element-wise path with the same result. No
+ * workspace. Every argument is checked before any device call. */
+int ksp_compress_weights(int device, void *stream, const float *weights, uint8_t *weights8,
+                         float *weights_channel, int channels, int baselines,
+                         int weights_stride, int weights8_stride);
+
 /* ---- masked_gaussian_filter (reference rfi/twodflag.py:254-400) ----
  * Images [images][rows][cols] of float32 (itemsize 4) or float64 (itemsize 8); data, flags
  * (uint8, non-zero = flagged) and out share image_stride and row_stride, in elements

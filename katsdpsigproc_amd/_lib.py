@@ -181,6 +181,9 @@ SIGNATURES = {
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
         c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
     ],
+    "ksp_compress_weights": [
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+    ],
     "ksp_launch_function": [
         c_int, c_void_p, c_void_p, POINTER(ctypes.c_uint), POINTER(ctypes.c_uint), ctypes.c_uint,
         POINTER(c_void_p),

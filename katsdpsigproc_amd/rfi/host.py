@@ -535,6 +535,66 @@ class PrepareHost:
         return vis, input_flags, weights
 
 
+class CompressWeightsHost:
+    """Float32 weights as one byte per sample and one float32 per channel: what a pipeline
+    sends on instead of 4 bytes per sample. No reference counterpart; this class is the
+    definition that the device operation (:class:`.ingest.CompressWeightsTemplate`) matches
+    bit for bit. For row ``c``, every float step one float32 operation, rounded once::
+
+        ok(w) = w > 0 and w < +inf
+        m     = max over b of (ok(w[c, b]) ? w[c, b] : +0.0)       (+0.0 if no element is ok)
+        wc    = m / 255                                  -> weights_channel[c]
+        t     = w[c, b] / wc                             (IEEE, also when wc == 0)
+        q     = not (w[c, b] > 0) ? 0 : (t >= 255 ? 255 : max(1, rint(t)))   -> weights8[c, b]
+
+    (``rint`` rounds ties to even.) What follows from it:
+
+    * The byte is 0 exactly where the weight is not positive: zero, -0.0, negative or NaN,
+      which keeps :class:`AveragerHost`'s convention that weight 0 means "no data". A positive
+      weight never becomes 0: that is what the ``max(1, ...)`` is for.
+    * ``+inf`` takes no part in the maximum and becomes 255.
+    * There is no special case for ``wc == 0``, which happens when no element is ok or when
+      ``m / 255`` underflows to zero: ``w / 0`` is ``+inf``, so every positive weight becomes
+      255, and ``255 * wc`` is 0. No NaN can arise in ``t`` for ``w > 0``.
+    * When ``wc`` is a normal number (``m >= 2**-118``) the row's maximum maps to 255, and for
+      every finite positive ``w`` of the row ``|q * wc - w| <= wc / 2`` to within rounding
+      when ``q > 1`` and ``|q * wc - w| <= wc`` when ``q == 1``.
+    * With a denormal ``wc`` the quotient ``m / wc`` ranges from 128 to 382; the result is
+      then simply what the formula gives.
+    """
+
+    def __call__(self, weights: np.ndarray):
+        """``(weights8, weights_channel)``: uint8 (channels, baselines) and float32
+        (channels,) for float32 `weights` (channels, baselines), both at least 1.
+        ``ValueError``, naming the argument, for a wrong dtype, rank or shape."""
+        weights = _check_array("weights", weights, np.float32, "(channels, baselines)",
+                               lambda s: len(s) == 2 and s[0] >= 1 and s[1] >= 1)  # fmt: skip
+        with np.errstate(all="ignore"):
+            ok = (weights > 0) & (weights < np.inf)
+            m = np.where(ok, weights, np.float32(0)).max(axis=1)
+            weights_channel = m / np.float32(255)
+            t = weights / weights_channel[:, np.newaxis]
+            positive = weights > 0
+            # (rint only of what is used: a t that is NaN or 255 and more is replaced first)
+            rounded = np.rint(np.where(positive & (t < 255), t, np.float32(1)))
+            q = np.where(t >= 255, np.float32(255), np.maximum(rounded, np.float32(1)))
+            weights8 = np.where(positive, q, np.float32(0)).astype(np.uint8)
+        assert weights_channel.dtype == np.float32 and t.dtype == np.float32
+        return weights8, weights_channel
+
+    @staticmethod
+    def expand(weights8: np.ndarray, weights_channel: np.ndarray) -> np.ndarray:
+        """The consumer's side: ``float32(weights8) * weights_channel`` of its row, float32
+        (channels, baselines). ``ValueError`` unless `weights8` is uint8 (channels, baselines)
+        and `weights_channel` float32 (channels,)."""
+        weights8 = _check_array("weights8", weights8, np.uint8, "(channels, baselines)",
+                                lambda s: len(s) == 2)  # fmt: skip
+        weights_channel = _check_array("weights_channel", weights_channel, np.float32,
+                                       "(channels,)", lambda s: s == weights8.shape[:1])  # fmt: skip
+        with np.errstate(all="ignore"):
+            return weights8.astype(np.float32) * weights_channel[:, np.newaxis]
+
+
 class FlaggerHost(AbstractFlaggerHost):
     """background -> noise estimate -> threshold (reference rfi/host.py:257-273)."""
 

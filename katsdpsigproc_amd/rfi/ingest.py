@@ -1,7 +1,10 @@
 """The step in front of the flagging chain: a correlator's integer dump, as it arrives, to the
 ``vis``, ``input_flags`` and ``weights`` that :mod:`.device` takes as inputs, in one kernel
 launch (no reference counterpart). :class:`.host.PrepareHost` is the definition; the kernel
-matches it bit for bit. The classes follow DESIGN.md, "Adding an operation".
+matches it bit for bit. And the step behind it: the float32 ``weights`` that
+:class:`.device.Finalise` leaves to one byte per sample and one float32 per channel, again in
+one launch and bit for bit what :class:`.host.CompressWeightsHost` defines. The classes follow
+DESIGN.md, "Adding an operation".
 """
 
 from typing import Any, Mapping, Optional, Tuple
@@ -172,3 +175,88 @@ class PrepareHostFromDevice:
         outputs = ["vis", "input_flags"] + (["weights"] if template.weights else [])
         out = _native_op.run_once(fn, self.command_queue, inputs, outputs)
         return out[0], out[1], (out[2] if template.weights else None)
+
+
+class CompressWeightsTemplate(_native_op.NativeTemplate):
+    """The step behind the chain: the float32 ``weights`` that :class:`.device.Finalise`
+    leaves as one byte per sample (``weights8``) and one float32 per channel
+    (``weights_channel``, the row's largest weight divided by 255), in one kernel launch; see
+    :class:`host.CompressWeightsHost` for every step. The output of the chain is then 9 bytes
+    per sample and 4 per channel instead of 13 per sample.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    tuning
+        The kernel picks its launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.CompressWeightsHost
+    KERNEL = "ksp_compress_weights"
+
+    def __init__(self, context: AbstractContext,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        self._setup(context, tuning)
+
+
+class CompressWeights(_native_op.NativeOperation):
+    """Concrete :class:`CompressWeightsTemplate` (``ValueError`` if `channels` or `baselines`
+    is below 1).
+
+    .. rubric:: Slots
+
+    **weights** : channels x baselines, float32
+    **weights8** : channels x baselines, uint8
+    **weights_channel** : channels, float32
+
+    Every padded dimension is an object of its own, so ``weights`` can be compounded with
+    :class:`.device.Finalise`'s ``weights`` and take its padding.
+    """
+
+    def __init__(self, template: CompressWeightsTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        if channels < 1 or baselines < 1:
+            raise ValueError("channels and baselines must be at least 1")
+        self.slots["weights"] = accel.IOSlot((channels, accel.Dimension(baselines)), np.float32)
+        self.slots["weights8"] = accel.IOSlot((channels, accel.Dimension(baselines)), np.uint8)
+        self.slots["weights_channel"] = accel.IOSlot((accel.Dimension(channels),), np.float32)
+
+    def _run(self) -> None:
+        weights, weights8 = self.buffer("weights"), self.buffer("weights8")
+        self._launch(
+            weights.buffer,
+            weights8.buffer,
+            self.buffer("weights_channel").buffer,
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(weights.padded_shape[1]),
+            np.int32(weights8.padded_shape[1]),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        return self._parameters()
+
+
+CompressWeightsTemplate.operation_class = CompressWeights
+
+
+class CompressWeightsHostFromDevice:
+    """Make a :class:`CompressWeightsTemplate` callable like
+    :class:`host.CompressWeightsHost`: ``weights`` in, ``(weights8, weights_channel)`` out;
+    allocates on every call."""
+
+    def __init__(self, template: CompressWeightsTemplate,
+                 command_queue: AbstractCommandQueue) -> None:  # fmt: skip
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, weights: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        channels, baselines = weights.shape
+        fn = self.template.instantiate(self.command_queue, channels, baselines)
+        out = _native_op.run_once(fn, self.command_queue, {"weights": weights},
+                                  ["weights8", "weights_channel"])  # fmt: skip
+        return out[0], out[1]
