@@ -499,6 +499,39 @@ int ksp_compress_weights(int device, void *stream, const float *weights, uint8_t
                          float *weights_channel, int channels, int baselines,
                          int weights_stride, int weights8_stride);
 
+/* range_percentiles: per channel and per range of baselines, the [0, 100, 25, 75, 50] %
+ * amplitudes ("lower" element) of the samples that are neither NaN nor flagged under a mask,
+ * how many those are, and the OR of the range's flags, all ranges in one launch (no reference
+ * counterpart; bit for bit what rfi/host.py RangePercentilesHost computes; with nothing left
+ * out, what ksp_percentile5_float gives for the same column range).
+ * in: [channels][in_stride] float32 amplitudes (is_amplitude != 0) or complex64 (== 0), of
+ * which `baselines` are data; flags: uint8 [channels][flags_stride]. percentiles: float32
+ * [n_ranges * 5][out_stride], counts: uint32 [n_ranges][counts_stride], range_flags: uint8
+ * [n_ranges][range_flags_stride], of which `channels` per row are data. Strides in elements.
+ * ranges is a HOST pointer to n_ranges (1..16) pairs (start, stop) of ints with
+ * 0 <= start <= stop <= baselines and stop - start <= 16384; it is copied during the call.
+ * Ranges may be empty, overlap, repeat and come in any order. Per channel c and range r:
+ *   a[b] = in[c][b], or numpy's |in[c][b]| for complex64              (b in [start, stop));
+ *   kept = { b : a[b] is not NaN and (flags[c][b] & mask) == 0 },  n = size of kept;
+ *   counts[r][c] = n;  with K the kept a[b] in ascending order,
+ *   percentiles[5 r + 0 .. 5 r + 4][c] = K[0], K[n-1], K[(n-1)/4], K[3(n-1)/4], K[(n-1)/2],
+ *   five +0.0 when n == 0;  range_flags[r][c] = OR of flags[c][b] over ALL b of the range.
+ * flags and range_flags are both NULL (then mask must be 0 and flags_stride and
+ * range_flags_stride are ignored) or both given; mask is 0..255. float32 input must be
+ * non-negative with the sign bit clear, or NaN (+inf is an ordinary largest value); anything
+ * else gives an unspecified value in that range's percentiles and no access outside the
+ * arrays. Every output element inside [row * stride, row * stride + channels) is written on
+ * every call; elements beyond `channels` of an output row are never written, elements outside
+ * the ranges of an input row never read. 16-byte loads are taken where the first sample and
+ * first flag byte of a range in a row allow it; anything else goes element by element with
+ * the same result. One kernel launch, no workspace. channels == 0 returns 0. Every argument
+ * is checked before any device call. */
+int ksp_range_percentiles(int device, void *stream, const void *in, const unsigned char *flags,
+                          float *percentiles, unsigned *counts, unsigned char *range_flags,
+                          int channels, int baselines, int in_stride, int flags_stride,
+                          int out_stride, int counts_stride, int range_flags_stride,
+                          const int *ranges, int n_ranges, int is_amplitude, int mask);
+
 /* ---- masked_gaussian_filter (reference rfi/twodflag.py:254-400) ----
  * Images [images][rows][cols] of float32 (itemsize 4) or float64 (itemsize 8); data, flags
  * (uint8, non-zero = flagged) and out share image_stride and row_stride, in elements

@@ -184,6 +184,10 @@ SIGNATURES = {
     "ksp_compress_weights": [
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
     ],
+    "ksp_range_percentiles": [
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+        c_int, c_int, c_int, c_int, POINTER(c_int), c_int, c_int, c_int,
+    ],
     "ksp_launch_function": [
         c_int, c_void_p, c_void_p, POINTER(ctypes.c_uint), POINTER(ctypes.c_uint), ctypes.c_uint,
         POINTER(c_void_p),

@@ -13,7 +13,7 @@ and raise if the native library is missing.
 
 import warnings
 from abc import ABC, abstractmethod
-from typing import Optional
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -593,6 +593,138 @@ class CompressWeightsHost:
                                        "(channels,)", lambda s: s == weights8.shape[:1])  # fmt: skip
         with np.errstate(all="ignore"):
             return weights8.astype(np.float32) * weights_channel[:, np.newaxis]
+
+
+def check_ranges(ranges, baselines: Optional[int] = None) -> Tuple[Tuple[int, int], ...]:
+    """`ranges` as a tuple of 1 to :attr:`RangePercentilesHost.MAX_RANGES` pairs of ints
+    ``(start, stop)`` with ``0 <= start <= stop``, ``stop - start`` at most
+    :attr:`RangePercentilesHost.MAX_LENGTH` and, if `baselines` is given, ``stop <= baselines``
+    (``ValueError`` naming ``ranges`` otherwise)."""
+    try:
+        pairs = [tuple(pair) for pair in ranges]
+    except TypeError:
+        raise ValueError(f"ranges {ranges!r} is not a sequence of (start, stop) pairs") from None
+    if not 1 <= len(pairs) <= RangePercentilesHost.MAX_RANGES:
+        raise ValueError(f"ranges must hold 1..{RangePercentilesHost.MAX_RANGES} pairs, "
+                         f"not {len(pairs)}")  # fmt: skip
+    checked = []
+    for pair in pairs:
+        if len(pair) != 2 or any(isinstance(v, (bool, np.bool_))
+                                 or not isinstance(v, (int, np.integer)) for v in pair):  # fmt: skip
+            raise ValueError(f"ranges: {pair!r} is not a pair of integers (start, stop)")
+        start, stop = int(pair[0]), int(pair[1])
+        if not 0 <= start <= stop:
+            raise ValueError(f"ranges: ({start}, {stop}) does not satisfy 0 <= start <= stop")
+        if stop - start > RangePercentilesHost.MAX_LENGTH:
+            raise ValueError(f"ranges: ({start}, {stop}) is longer than "
+                             f"{RangePercentilesHost.MAX_LENGTH} columns")  # fmt: skip
+        if baselines is not None and stop > baselines:
+            raise ValueError(f"ranges: ({start}, {stop}) ends beyond the {baselines} baselines")
+        checked.append((start, stop))
+    return tuple(checked)
+
+
+def check_mask_byte(name: str, value) -> int:
+    """`value` as an int in 0..255 (``ValueError`` otherwise, ``TypeError`` for a value that
+    is not an integer)."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise TypeError(f"{name} {value!r} is not an integer")
+    if not 0 <= value <= 255:
+        raise ValueError(f"{name} {value} is outside 0..255")
+    return int(value)
+
+
+class RangePercentilesHost:
+    """The signal-display product of a dump: for every range of baselines (a group such as
+    "auto HH") and every channel, the 0/100/25/75/50 % amplitudes of the samples that carry
+    data, how many those are, and the OR of the group's flags. No reference counterpart; this
+    class is the definition that the device operation
+    (:class:`.ingest.RangePercentilesTemplate`) matches bit for bit. For channel ``c`` and
+    range ``(start, stop)`` number ``r``::
+
+        a[b]   = data[c, b] if float32, numpy.abs(data[c, b]) if complex64   (b in [start, stop))
+        kept   = { b : not isnan(a[b]) and (flags[c, b] & mask) == 0 }  (no flags: no second term)
+        K      = sort(a[kept]);  n = len(K)
+        counts[r, c]         = n
+        percentiles[r, :, c] = K[0], K[n-1], K[(n-1)//4], K[3*(n-1)//4], K[(n-1)//2]
+                               (five +0.0 when n == 0)
+        range_flags[r, c]    = OR of flags[c, b] over ALL b in [start, stop)  (0 if there are none)
+
+    The indices are those of ``numpy.percentile(K, [0, 100, 25, 75, 50], method="lower")``,
+    and the row order is that of the reference's ``Percentile5``; with nothing left out the
+    five rows of a range are what ``Percentile5`` gives for that ``column_range``.
+
+    Why samples are left out: a flagged sample is interference the flagger already found, and
+    a display whose "max" and "75 %" lines follow it hides the band underneath; a NaN is what
+    :class:`AveragerHost` never produces but a caller's own averaging may leave where there was
+    no data, and it must not count as "larger than everything". ``range_flags`` still reports
+    every flag of the group, kept or not.
+
+    float32 `data` must be non-negative with the sign bit clear, or NaN (the restriction of
+    ``Percentile5``, whose rank search the device shares). This class sorts whatever it is
+    given; the device gives an unspecified value in the percentiles of a range that holds a
+    negative value or ``-0.0`` (never an access outside the arrays). ``+inf`` is an ordinary
+    largest value.
+
+    Parameters
+    ----------
+    ranges
+        1 to 16 pairs ``(start, stop)``; they may be empty, overlap, repeat and come in any
+        order; at most 16384 columns each (:func:`check_ranges`)
+    mask
+        0..255: a sample with ``flags & mask != 0`` is left out; 0 leaves out NaN alone
+    """
+
+    MAX_RANGES = 16
+    MAX_LENGTH = 16384
+
+    def __init__(self, ranges, mask: int = 0) -> None:
+        self.ranges = check_ranges(ranges)
+        self.mask = check_mask_byte("mask", mask)
+
+    def __call__(self, data: np.ndarray, flags: Optional[np.ndarray] = None):
+        """``(percentiles, counts, range_flags)``: float32 (n_ranges, 5, channels), uint32
+        (n_ranges, channels) and uint8 (n_ranges, channels) -- ``None`` without `flags` -- for
+        float32 or complex64 `data` (channels, baselines), both at least 1, and optional uint8
+        `flags` of the same shape. ``TypeError`` for a non-zero mask without `flags`;
+        ``ValueError``, naming the argument, for a wrong dtype, rank or shape or a range that
+        ends beyond the baselines."""
+        data = np.asarray(data)
+        dtype = np.complex64 if data.dtype == np.complex64 else np.float32
+        data = _check_array("data", data, dtype, "(channels, baselines)",
+                            lambda s: len(s) == 2 and s[0] >= 1 and s[1] >= 1)  # fmt: skip
+        channels, baselines = data.shape
+        if flags is None:
+            if self.mask != 0:
+                raise TypeError(f"mask {self.mask:#x} was given but flags were not provided")
+        else:
+            flags = _check_array("flags", flags, np.uint8, "(channels, baselines)",
+                                 lambda s: s == data.shape)  # fmt: skip
+        check_ranges(self.ranges, baselines)
+        n_ranges = len(self.ranges)
+        percentiles = np.zeros((n_ranges, 5, channels), np.float32)
+        counts = np.zeros((n_ranges, channels), np.uint32)
+        range_flags = None if flags is None else np.zeros((n_ranges, channels), np.uint8)
+        rows = np.arange(channels)
+        for r, (start, stop) in enumerate(self.ranges):
+            if start == stop:
+                continue
+            with np.errstate(all="ignore"):
+                a = np.abs(data[:, start:stop]) if dtype == np.complex64 else data[:, start:stop]
+            assert a.dtype == np.float32
+            kept = ~np.isnan(a)
+            if flags is not None:
+                part = flags[:, start:stop]
+                kept &= (part & np.uint8(self.mask)) == 0
+                range_flags[r] = np.bitwise_or.reduce(part, axis=1)
+            n = kept.sum(axis=1)
+            counts[r] = n
+            # (NaN sorts last: the kept values are the first n of a sorted row)
+            ordered = np.sort(np.where(kept, a, np.float32(np.nan)), axis=1)
+            last = np.maximum(n - 1, 0)
+            for k, index in enumerate((0 * last, last, last // 4, 3 * last // 4, last // 2)):
+                percentiles[r, k] = np.where(n > 0, ordered[rows, index], np.float32(0))
+        return percentiles, counts, range_flags
 
 
 class FlaggerHost(AbstractFlaggerHost):

@@ -3,10 +3,14 @@
 launch (no reference counterpart). :class:`.host.PrepareHost` is the definition; the kernel
 matches it bit for bit. And the step behind it: the float32 ``weights`` that
 :class:`.device.Finalise` leaves to one byte per sample and one float32 per channel, again in
-one launch and bit for bit what :class:`.host.CompressWeightsHost` defines. The classes follow
+one launch and bit for bit what :class:`.host.CompressWeightsHost` defines. And the step that
+closes it: the percentiles of the averaged amplitudes over ranges of baselines, flagged and NaN
+samples left out, with a count and the OR of the flags per range and channel: all ranges in one
+launch, bit for bit what :class:`.host.RangePercentilesHost` defines. The classes follow
 DESIGN.md, "Adding an operation".
 """
 
+import ctypes
 from typing import Any, Mapping, Optional, Tuple
 
 import numpy as np
@@ -260,3 +264,146 @@ class CompressWeightsHostFromDevice:
         out = _native_op.run_once(fn, self.command_queue, {"weights": weights},
                                   ["weights8", "weights_channel"])  # fmt: skip
         return out[0], out[1]
+
+
+class RangePercentilesTemplate(_native_op.NativeTemplate):
+    """The step that closes the chain: the signal-display product of the ``vis`` and ``flags``
+    that :class:`.device.Finalise` (or the flagger) leaves. For every range of baselines and
+    every channel, the 0/100/25/75/50 % amplitudes of the samples that are neither NaN nor
+    flagged under `mask`, the number of those samples and the OR of the range's flags: every
+    range in one kernel launch; see :class:`host.RangePercentilesHost` for every step. With
+    nothing left out, the five rows of a range are what :class:`..percentile.Percentile5` gives
+    for that ``column_range``.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    is_amplitude
+        ``True``: `data` is float32 amplitudes (non-negative with the sign bit clear, or NaN);
+        ``False``: complex64
+    use_flags
+        ``True``: there are a `flags` and a `range_flags` slot
+    mask
+        As for :class:`host.RangePercentilesHost` (same errors); ``ValueError`` if it is not 0
+        and `use_flags` is false
+    tuning
+        The kernel picks its launch geometry from the ranges: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.RangePercentilesHost
+    KERNEL = "ksp_range_percentiles"
+
+    def __init__(self, context: AbstractContext, is_amplitude: bool = False,
+                 use_flags: bool = True, mask: int = 0,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        self.is_amplitude = bool(is_amplitude)
+        self.use_flags = bool(use_flags)
+        self.mask = host.check_mask_byte("mask", mask)
+        if self.mask != 0 and not self.use_flags:
+            raise ValueError(f"mask {self.mask:#x} needs use_flags")
+        self._setup(context, tuning)
+
+
+class RangePercentiles(_native_op.NativeOperation):
+    """Concrete :class:`RangePercentilesTemplate` (``ValueError`` if `channels` or `baselines`
+    is below 1, or for `ranges` that :func:`host.check_ranges` rejects for `baselines`).
+
+    .. rubric:: Slots
+
+    **data** : channels x baselines, float32 (``is_amplitude``) or complex64
+    **flags** : channels x baselines, uint8 (only with ``use_flags``)
+    **percentiles** : n_ranges x 5 x channels, float32, rows [0, 100, 25, 75, 50] %
+    **counts** : n_ranges x channels, uint32
+    **range_flags** : n_ranges x channels, uint8 (only with ``use_flags``)
+
+    Every padded dimension is an object of its own, so ``data`` and ``flags`` can be
+    compounded with :class:`.device.Finalise`'s ``vis`` and ``flags`` (or the flagger's) and
+    take their padding.
+    """
+
+    def __init__(self, template: RangePercentilesTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int, ranges,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        if channels < 1 or baselines < 1:
+            raise ValueError("channels and baselines must be at least 1")
+        self.ranges = host.check_ranges(ranges, baselines)
+        n_ranges = len(self.ranges)
+        # a host array the launcher copies during the call
+        self._ranges = (ctypes.c_int * (2 * n_ranges))(*[v for pair in self.ranges for v in pair])
+
+        def exact(size: int) -> accel.Dimension:
+            return accel.Dimension(size, exact=True)
+
+        dtype = np.float32 if template.is_amplitude else np.complex64
+        self.slots["data"] = accel.IOSlot((channels, accel.Dimension(baselines)), dtype)
+        if template.use_flags:
+            self.slots["flags"] = accel.IOSlot((channels, accel.Dimension(baselines)), np.uint8)
+        self.slots["percentiles"] = accel.IOSlot(
+            (exact(n_ranges), exact(5), accel.Dimension(channels)), np.float32)  # fmt: skip
+        self.slots["counts"] = accel.IOSlot(
+            (exact(n_ranges), accel.Dimension(channels)), np.uint32)  # fmt: skip
+        if template.use_flags:
+            self.slots["range_flags"] = accel.IOSlot(
+                (exact(n_ranges), accel.Dimension(channels)), np.uint8)  # fmt: skip
+
+    def _run(self) -> None:
+        template = self.template
+        data, percentiles, counts = (self.buffer(name) for name in ("data", "percentiles", "counts"))
+        flags = self.buffer("flags") if template.use_flags else None
+        range_flags = self.buffer("range_flags") if template.use_flags else None
+        self._launch(
+            data.buffer,
+            flags.buffer if flags is not None else None,
+            percentiles.buffer,
+            counts.buffer,
+            range_flags.buffer if range_flags is not None else None,
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(data.padded_shape[1]),
+            np.int32(flags.padded_shape[1] if flags is not None else 0),
+            np.int32(percentiles.padded_shape[2]),
+            np.int32(counts.padded_shape[1]),
+            np.int32(range_flags.padded_shape[1] if range_flags is not None else 0),
+            self._ranges,
+            np.int32(len(self.ranges)),
+            np.int32(template.is_amplitude),
+            np.int32(template.mask),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        template = self.template
+        return self._parameters(
+            is_amplitude=template.is_amplitude,
+            use_flags=template.use_flags,
+            mask=template.mask,
+            ranges=[list(pair) for pair in self.ranges],
+        )
+
+
+RangePercentilesTemplate.operation_class = RangePercentiles
+
+
+class RangePercentilesHostFromDevice:
+    """Make a :class:`RangePercentilesTemplate` callable like
+    :class:`host.RangePercentilesHost`: ``(data, flags=None)`` in, ``(percentiles, counts,
+    range_flags or None)`` out; allocates on every call. ``TypeError`` unless `flags` is given
+    exactly when the template has ``use_flags``."""
+
+    def __init__(self, template: RangePercentilesTemplate, command_queue: AbstractCommandQueue,
+                 ranges) -> None:  # fmt: skip
+        self.template = template
+        self.command_queue = command_queue
+        self.ranges = host.check_ranges(ranges)
+
+    def __call__(self, data: np.ndarray, flags: Optional[np.ndarray] = None
+                 ) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:  # fmt: skip
+        template = self.template
+        _native_op.check_optional(flags, template.use_flags, "flags")
+        channels, baselines = data.shape
+        fn = template.instantiate(self.command_queue, channels, baselines, self.ranges)
+        outputs = ["percentiles", "counts"] + (["range_flags"] if template.use_flags else [])
+        out = _native_op.run_once(fn, self.command_queue, {"data": data, "flags": flags}, outputs)
+        return out[0], out[1], (out[2] if template.use_flags else None)
