@@ -21,7 +21,9 @@
 // other grid dimensions. When every pointer and every row start is 16-byte aligned, a lane whose
 // run lies wholly inside the row moves it with 16-byte loads and stores; the run at the end of
 // a row, and every run of an unaligned call, goes element by element and touches only
-// elements inside the row: padding is neither read nor written.
+// elements inside the row: padding is neither read nor written. (The run of run16.h, by hand:
+// written on its helpers, with the arithmetic stated once, both kernels were slower on the
+// 16-byte path, profiles/run16.md.)
 //
 // Traffic per sample: accumulate reads 8 (vis) + 1 (flags) + 4 (weights) and
 // reads and writes 8 + 4 + 1 of accumulators: 39 bytes, 35 without weights, plus one byte for
@@ -258,12 +260,6 @@ __global__ __launch_bounds__(AVG_THREADS) void average_finalise_kernel(
     }
 }
 
-// 16-byte accesses to an array's rows; an array that is not given (NULL) does not object
-static bool avg_aligned16(const void *p, long long stride, int itemsize)
-{
-    return p == nullptr || ksp_rows_aligned(p, stride, itemsize);
-}
-
 template <bool HAS_W>
 static void avg_launch_accumulate(int mode, dim3 grid, hipStream_t stream, const float2 *vis,
                                   const uint8_t *flags, const float *weights,
@@ -320,12 +316,13 @@ extern "C" int ksp_average_accumulate(int device, void *stream, const void *vis,
     const long long groups = (runs + AVG_THREADS - 1) / AVG_THREADS;
     KSP_REQUIRE(groups <= 0x7fffffffll, "array too large for one launch");
     const int aligned =
-        avg_aligned16(vis, vis_stride, 8) && avg_aligned16(flags, flags_stride, 1) &&
-        avg_aligned16(weights, weights_stride, 4) &&
-        (input_flags_mode != 2 || avg_aligned16(input_flags, input_flags_stride, 1)) &&
-        avg_aligned16(acc_vis, acc_vis_stride, 8) &&
-        avg_aligned16(acc_weights, acc_weights_stride, 4) &&
-        avg_aligned16(acc_flags, acc_flags_stride, 1);
+        ksp_rows_aligned_if_given(vis, vis_stride, 8) &&
+        ksp_rows_aligned_if_given(flags, flags_stride, 1) &&
+        ksp_rows_aligned_if_given(weights, weights_stride, 4) &&
+        (input_flags_mode != 2 || ksp_rows_aligned_if_given(input_flags, input_flags_stride, 1)) &&
+        ksp_rows_aligned_if_given(acc_vis, acc_vis_stride, 8) &&
+        ksp_rows_aligned_if_given(acc_weights, acc_weights_stride, 4) &&
+        ksp_rows_aligned_if_given(acc_flags, acc_flags_stride, 1);
 
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
@@ -375,11 +372,12 @@ extern "C" int ksp_average_finalise(int device, void *stream, void *acc_vis, flo
     const long long groups = (runs + AVG_THREADS - 1) / AVG_THREADS;
     KSP_REQUIRE(groups <= 0x7fffffffll, "array too large for one launch");
     const int aligned =
-        avg_aligned16(acc_vis, acc_vis_stride, 8) &&
-        avg_aligned16(acc_weights, acc_weights_stride, 4) &&
-        avg_aligned16(acc_flags, acc_flags_stride, 1) && avg_aligned16(out_vis, out_vis_stride, 8) &&
-        avg_aligned16(out_weights, out_weights_stride, 4) &&
-        avg_aligned16(out_flags, out_flags_stride, 1);
+        ksp_rows_aligned_if_given(acc_vis, acc_vis_stride, 8) &&
+        ksp_rows_aligned_if_given(acc_weights, acc_weights_stride, 4) &&
+        ksp_rows_aligned_if_given(acc_flags, acc_flags_stride, 1) &&
+        ksp_rows_aligned_if_given(out_vis, out_vis_stride, 8) &&
+        ksp_rows_aligned_if_given(out_weights, out_weights_stride, 4) &&
+        ksp_rows_aligned_if_given(out_flags, out_flags_stride, 1);
 
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;

@@ -14,12 +14,12 @@
 // order like unsigned integers, so the reduction is an integer maximum: exact, the same in any
 // order, and no NaN or denormal rule of a floating-point maximum has a say.
 //
-// Layout. Both arrays are [channels][stride] with baselines contiguous, as in average.hip, and
-// a lane owns runs of CW_RUN = 16 adjacent baselines: 64 bytes of weights (four 16-byte loads)
-// and 16 result bytes (one 16-byte store). A row needs its maximum before any byte of it can be
-// written, so a row belongs to a team of wavefronts that keeps the row's weights in registers
-// between the reduction and the quantisation; the array is read once. The team is chosen from
-// the row length (cw_path, the only place that knows the limits):
+// Layout. Both arrays are [channels][stride] with baselines contiguous, and a lane owns runs of
+// 16 adjacent baselines (run16.h): 64 bytes of weights and 16 result bytes. A row needs its
+// maximum before any byte of it can be written, so a row belongs to a team of wavefronts that
+// keeps the row's weights in registers between the reduction and the quantisation; the array is
+// read once. The team is chosen from the row length (cw_path, the only place that knows the
+// limits):
 //
 //   baselines <=  1024   1 wavefront, 1 run per lane; a 256-thread workgroup holds 4 rows,
 //                        and the reduction is shuffles alone (no LDS, no barrier)
@@ -36,15 +36,13 @@
 // the order of workgroups.
 //
 // The 16-byte loads apply when weights and its row starts are multiples of 16 bytes, the
-// 16-byte stores when weights8 and its row starts are. The ragged run at the end of a row, and
-// every run of an array that is not aligned so, go element by element. Padding of weights is
-// never read, padding of weights8 never written.
+// 16-byte stores when weights8 and its row starts are: one flag each.
 //
 // Traffic per sample: 4 bytes read, 1 written (8 read beyond 32768 baselines), and 4 bytes
 // per row.
 #include "launch.h"
+#include "run16.h"
 
-#define CW_RUN 16
 #define CW_ALIGNED_LOADS 1
 #define CW_ALIGNED_STORES 2
 // the longest row whose weights stay in registers, and the lengths below it at which the team
@@ -55,30 +53,11 @@
 #define CW_RESIDENT_MAX 32768
 #define CW_LONG_THREADS 1024
 
-// The `valid` (<= CW_RUN, may be <= 0) weights at `w`; the rest of v is +0, which takes no part
-// in the maximum and is never stored.
-__device__ __forceinline__ void cw_load(const float *w, int valid, bool wide, float (&v)[CW_RUN])
-{
-    if (wide && valid >= CW_RUN) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const float4 t = reinterpret_cast<const float4 *>(w)[q];
-            v[4 * q] = t.x;
-            v[4 * q + 1] = t.y;
-            v[4 * q + 2] = t.z;
-            v[4 * q + 3] = t.w;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < CW_RUN; i++) v[i] = i < valid ? w[i] : 0.0f;
-    }
-}
-
 // max(m, bit patterns of the weights of v that are positive and finite)
-__device__ __forceinline__ unsigned cw_max(unsigned m, const float (&v)[CW_RUN])
+__device__ __forceinline__ unsigned cw_max(unsigned m, const float (&v)[KSP_RUN])
 {
 #pragma unroll
-    for (int i = 0; i < CW_RUN; i++) {
+    for (int i = 0; i < KSP_RUN; i++) {
         const bool ok = v[i] > 0.0f && v[i] < __builtin_inff();
         m = max(m, ok ? __float_as_uint(v[i]) : 0u);
     }
@@ -95,8 +74,9 @@ __device__ __forceinline__ unsigned cw_quantise(float w, float wc)
     return w > 0.0f ? (unsigned)q : 0u;
 }
 
+// The bytes of the weights of v, stored as far as they are `valid`
 __device__ __forceinline__ void cw_store(uint8_t *out, int valid, bool wide,
-                                         const float (&v)[CW_RUN], float wc)
+                                         const float (&v)[KSP_RUN], float wc)
 {
     unsigned word[4];
 #pragma unroll
@@ -105,27 +85,14 @@ __device__ __forceinline__ void cw_store(uint8_t *out, int valid, bool wide,
 #pragma unroll
         for (int k = 0; k < 4; k++) word[q] |= cw_quantise(v[4 * q + k], wc) << (8 * k);
     }
-    if (wide && valid >= CW_RUN) {
-        *reinterpret_cast<uint4 *>(out) = make_uint4(word[0], word[1], word[2], word[3]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < CW_RUN; i++)
-            if (i < valid) out[i] = (uint8_t)(word[i / 4] >> (8 * (i % 4)));
-    }
-}
-
-__device__ __forceinline__ unsigned cw_wave_max(unsigned m)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
-    return m;
+    ksp_run_store_bytes(out, valid, wide, ksp_run_bytes{word[0], word[1], word[2], word[3]});
 }
 
 // The maximum over the TEAM wavefronts of a workgroup (TEAM > 1: the whole workgroup is one team)
 template <int TEAM>
 __device__ __forceinline__ unsigned cw_team_max(unsigned m)
 {
-    m = cw_wave_max(m);
+    m = ksp_wave_max(m);
     if constexpr (TEAM > 1) {
         __shared__ unsigned wave_max[TEAM];
         if (threadIdx.x % KSP_WAVE == 0) wave_max[threadIdx.x / KSP_WAVE] = m;
@@ -139,7 +106,7 @@ __device__ __forceinline__ unsigned cw_team_max(unsigned m)
 #define CW_WAVES(team) ((team) > 4 ? (team) : 4)
 
 // A team of TEAM wavefronts per row, RUNS runs per lane, the row's weights in registers.
-// Needs baselines <= TEAM * 64 * RUNS * CW_RUN.
+// Needs baselines <= TEAM * 64 * RUNS * KSP_RUN.
 template <int TEAM, int RUNS>
 __global__ __launch_bounds__(CW_WAVES(TEAM) * KSP_WAVE) void compress_weights_kernel(
     const float *__restrict__ weights, uint8_t *__restrict__ weights8,
@@ -155,12 +122,12 @@ __global__ __launch_bounds__(CW_WAVES(TEAM) * KSP_WAVE) void compress_weights_ke
     const float *w = weights + row * weights_stride;
     uint8_t *out = weights8 + row * weights8_stride;
 
-    float v[RUNS][CW_RUN];
+    float v[RUNS][KSP_RUN];
     unsigned m = 0;
 #pragma unroll
     for (int r = 0; r < RUNS; r++) {
-        const int col0 = (r * LANES + lane) * CW_RUN;
-        cw_load(w + col0, baselines - col0, aligned & CW_ALIGNED_LOADS, v[r]);
+        const int col0 = (r * LANES + lane) * KSP_RUN;
+        ksp_run_load(w + col0, baselines - col0, aligned & CW_ALIGNED_LOADS, v[r], 0.0f);
     }
 #pragma unroll
     for (int r = 0; r < RUNS; r++) m = cw_max(m, v[r]);
@@ -169,7 +136,7 @@ __global__ __launch_bounds__(CW_WAVES(TEAM) * KSP_WAVE) void compress_weights_ke
     if (lane == 0) weights_channel[row] = wc;
 #pragma unroll
     for (int r = 0; r < RUNS; r++) {
-        const int col0 = (r * LANES + lane) * CW_RUN;
+        const int col0 = (r * LANES + lane) * KSP_RUN;
         cw_store(out + col0, baselines - col0, aligned & CW_ALIGNED_STORES, v[r], wc);
     }
 }
@@ -184,23 +151,23 @@ __global__ __launch_bounds__(CW_LONG_THREADS) void compress_weights_long_kernel(
     const float *w = weights + row * weights_stride;
     uint8_t *out = weights8 + row * weights8_stride;
     // (columns as 64-bit numbers: the last lanes' first column may lie beyond 2^31)
-    const long long first = (long long)threadIdx.x * CW_RUN;
-    const long long step = (long long)CW_LONG_THREADS * CW_RUN;
+    const long long first = (long long)threadIdx.x * KSP_RUN;
+    const long long step = (long long)CW_LONG_THREADS * KSP_RUN;
 
     unsigned m = 0;
     for (long long col0 = first; col0 < baselines; col0 += step) {
-        float v[CW_RUN];
-        cw_load(w + col0, (int)min((long long)CW_RUN, baselines - col0),
-                aligned & CW_ALIGNED_LOADS, v);
+        float v[KSP_RUN];
+        ksp_run_load(w + col0, (int)min((long long)KSP_RUN, baselines - col0),
+                     aligned & CW_ALIGNED_LOADS, v, 0.0f);
         m = cw_max(m, v);
     }
     m = cw_team_max<CW_LONG_THREADS / KSP_WAVE>(m);
     const float wc = __fdiv_rn(__uint_as_float(m), 255.0f);
     if (threadIdx.x == 0) weights_channel[row] = wc;
     for (long long col0 = first; col0 < baselines; col0 += step) {
-        const int valid = (int)min((long long)CW_RUN, baselines - col0);
-        float v[CW_RUN];
-        cw_load(w + col0, valid, aligned & CW_ALIGNED_LOADS, v);
+        const int valid = (int)min((long long)KSP_RUN, baselines - col0);
+        float v[KSP_RUN];
+        ksp_run_load(w + col0, valid, aligned & CW_ALIGNED_LOADS, v, 0.0f);
         cw_store(out + col0, valid, aligned & CW_ALIGNED_STORES, v, wc);
     }
 }

@@ -35,10 +35,10 @@
 // run. Sums wrap modulo 2^32 (only reachable with accumulate, or more than 2^32 - 1 rows
 // or columns, which the int arguments exclude).
 //
-// Unaligned input (flags or stride not a multiple of 16) and the lanes at the right-hand
-// edge, where fewer than 16 columns are left, load byte by byte and only bytes inside
-// the row: padding is never read, let alone counted.
+// The 16 bytes of a lane are a run of run16.h: unaligned input and the lanes at the right-hand
+// edge load byte by byte, and padding is never read, let alone counted.
 #include "launch.h"
+#include "run16.h"
 
 #define FC_THREADS 256
 #define FC_TILE_COLS (FC_THREADS * 16)
@@ -60,30 +60,21 @@ __device__ __forceinline__ unsigned fc_nonzero_bytes(unsigned w, unsigned mask4,
     return ((t | ((t & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u;
 }
 
-// The 16 bytes of one row that a lane owns; bytes at and beyond `valid` read as zero.
-template <bool FULL>
-__device__ __forceinline__ uint4 fc_load(const uint8_t *p, int valid)
-{
-    if (FULL) return *reinterpret_cast<const uint4 *>(p);
-    unsigned w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < 16; i++)
-        if (i < valid) w[i / 4] |= (unsigned)p[i] << (8 * (i % 4));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// UNROLL (even) rows are in flight per lane.
+// UNROLL (even) rows are in flight per lane. FULL: every lane of the wavefront has all 16 bytes
+// of its run, on 16-byte boundaries.
 template <int NM, bool SINGLE_BIT, bool FULL, int UNROLL>
 __device__ __forceinline__ void fc_walk(const uint8_t *base, long long stride, int nrows, int valid,
                                         const fc_masks &masks, unsigned (&acc)[NM][4],
                                         unsigned (*lds_rows)[FC_MAX_TILE_ROWS / 2], int lane)
 {
     for (int r = 0; r < nrows; r += UNROLL) {
-        uint4 v[UNROLL];
+        ksp_run_bytes v[UNROLL];
 #pragma unroll
         for (int u = 0; u < UNROLL; u++) {
-            v[u] = make_uint4(0, 0, 0, 0);
-            if (r + u < nrows) v[u] = fc_load<FULL>(base + (long long)(r + u) * stride, valid);
+            v[u] = ksp_run_bytes{0, 0, 0, 0};
+            if (r + u < nrows)
+                v[u] = ksp_run_load_bytes(base + (long long)(r + u) * stride,
+                                          FULL ? KSP_RUN : valid, FULL);
         }
 #pragma unroll
         for (int m = 0; m < NM; m++) {
@@ -93,12 +84,11 @@ __device__ __forceinline__ void fc_walk(const uint8_t *base, long long stride, i
                 unsigned pair = 0;
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
-                    const unsigned w[4] = {v[u + h].x, v[u + h].y, v[u + h].z, v[u + h].w};
                     unsigned count = 0;
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
-                        const unsigned nz =
-                            fc_nonzero_bytes<SINGLE_BIT>(w[k], masks.mask4[m], masks.shift[m]);
+                        const unsigned nz = fc_nonzero_bytes<SINGLE_BIT>(
+                            v[u + h][k], masks.mask4[m], masks.shift[m]);
                         acc[m][k] += nz;
                         count += __builtin_popcount(nz);
                     }

@@ -312,6 +312,20 @@ __device__ __forceinline__ float ksp_wave_min(float v)
     return v;
 }
 
+__device__ __forceinline__ unsigned ksp_wave_max(unsigned v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, off, 64));
+    return v;
+}
+
+__device__ __forceinline__ unsigned ksp_wave_min(unsigned v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, off, 64));
+    return v;
+}
+
 __device__ __forceinline__ double ksp_wave_max(double v)
 {
 #pragma unroll

@@ -30,6 +30,12 @@ inline bool ksp_rows_aligned(const void *ptr, long long stride, int elem_bytes, 
     return (uintptr_t)ptr % bytes == 0 && stride * elem_bytes % bytes == 0;
 }
 
+// The same for an optional array: one that is not given (NULL) does not object.
+inline bool ksp_rows_aligned_if_given(const void *ptr, long long stride, int elem_bytes)
+{
+    return ptr == nullptr || ksp_rows_aligned(ptr, stride, elem_bytes);
+}
+
 // One value per device, for what is set up or queried once per device: T() means "not yet".
 // A device outside 0 .. 63 has no slot: get() says "not yet" every time and set() does
 // nothing, so its caller does the work on every call. Static storage (zero-initialised).

@@ -129,9 +129,7 @@ __device__ __forceinline__ float wave_median_nonzero(const unsigned (&u)[64], in
             unsigned m = 0;
 #pragma unroll
             for (int i = 0; i < 64; i++) m = max(m, u[i] < pat ? u[i] : 0u);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
-            prev = __uint_as_float(m);
+            prev = __uint_as_float(ksp_wave_max(m));
         }
         result = __fmul_rn(__fadd_rn(result, prev), 0.5f);
     }

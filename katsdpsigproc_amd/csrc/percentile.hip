@@ -124,11 +124,8 @@ __global__ __launch_bounds__(256) void percentile5_wave_kernel(const void *__res
         }
         key[i] = k;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, off, 64));
-        kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, off, 64));
-    }
+    kmin = ksp_wave_min(kmin);
+    kmax = ksp_wave_max(kmax);
     unsigned hi[32], lo[32];  // inverted planes of key bits 16..31 / 0..15
 #pragma unroll
     for (int i = 0; i < 32; i++) {

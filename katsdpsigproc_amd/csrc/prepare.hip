@@ -38,7 +38,8 @@
 // are multiples of 16 bytes and vis_in is a multiple of 8 (its row stride is in pairs). The
 // ragged run at the end of a row, and every run of a call that is not aligned so, go element
 // by element with 4-byte loads. Padding of the outputs is never written, padding of vis_in
-// never read.
+// never read. (The run of run16.h, by hand: written on its helpers, with the arithmetic stated
+// once, the instances without weights were slower on the 16-byte path, profiles/run16.md.)
 //
 // Traffic per sample: 8 bytes gathered, 8 + 1 written, 4 more with weights.
 #include <limits.h>
@@ -232,10 +233,10 @@ extern "C" int ksp_prepare(int device, void *stream, const int32_t *vis_in, cons
     KSP_REQUIRE(groups <= 0x7fffffffll, "array too large for one launch");
     const int aligned =
         (uintptr_t)vis_in % 8 == 0 && ksp_rows_aligned(source, 0, 4) &&
-        (auto_source == nullptr || ksp_rows_aligned(auto_source, 0, 4)) &&
+        ksp_rows_aligned_if_given(auto_source, 0, 4) &&
         ksp_rows_aligned(vis, vis_stride, 8) &&
         ksp_rows_aligned(input_flags, input_flags_stride, 1) &&
-        (weights == nullptr || ksp_rows_aligned(weights, weights_stride, 4));
+        ksp_rows_aligned_if_given(weights, weights_stride, 4);
 
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;

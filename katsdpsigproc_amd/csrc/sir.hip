@@ -42,14 +42,15 @@
 // line of up to 4096 samples is read once and written once. Longer lines take segments the way
 // axis 0 takes panels: a forward pass, then last to first.
 //
-// Unaligned input (odd pointer or stride for axis 0, not multiples of 16 for axis 1) and the
-// lanes at the ragged end of a row load and store byte by byte, and only bytes inside the
-// row: padding is neither read nor written.
+// Unaligned input (odd pointer or stride for axis 0, not multiples of 16 for axis 1, whose
+// leaves are runs of run16.h) and the lanes at the ragged end of a row load and store byte by
+// byte, and only bytes inside the row: padding is neither read nor written.
 #include <limits.h>
 
 #include <utility>
 
 #include "launch.h"
+#include "run16.h"
 
 #define SIR_MAX_LINE 262144
 #define SIR_LEAF 16
@@ -398,30 +399,6 @@ __global__ __launch_bounds__(SIR0_THREADS) void sir_columns_kernel(
 }
 
 // ---------------------------------------------------------------------------- axis 1
-// The 16 bytes of a line that a thread owns; bytes at and beyond `valid` read as zero.
-template <bool ALIGNED>
-__device__ __forceinline__ uint4 sir1_load(const uint8_t *p, int valid)
-{
-    if (ALIGNED && valid == 16) return *reinterpret_cast<const uint4 *>(p);
-    unsigned w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < 16; i++)
-        if (i < valid) w[i / 4] |= (unsigned)p[i] << (8 * (i % 4));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-template <bool ALIGNED>
-__device__ __forceinline__ void sir1_store(uint8_t *p, int valid, const unsigned (&w)[4])
-{
-    if (ALIGNED && valid == 16) {
-        *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i++)
-        if (i < valid) p[i] = (uint8_t)(w[i / 4] >> (8 * (i % 4)));
-}
-
 __device__ __forceinline__ unsigned sir1_fbits(const unsigned (&w)[4], unsigned mask)
 {
     unsigned fbits = 0;
@@ -480,7 +457,7 @@ __global__ __launch_bounds__(SIR1_THREADS) void sir_rows_kernel(uint8_t *__restr
     const auto load = [&](int segment, unsigned (&w)[4], int &valid) {
         const int col0 = segment * SIR1_SEGMENT + tid * SIR_LEAF;  // < 2^18 + 2^12
         valid = max(0, min(SIR_LEAF, cols - col0));
-        const uint4 v = sir1_load<ALIGNED>(line + col0, valid);  // (valid == 0: not dereferenced)
+        const ksp_run_bytes v = ksp_run_load_bytes(line + col0, valid, ALIGNED);
         w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
         return col0;
     };
@@ -519,7 +496,7 @@ __global__ __launch_bounds__(SIR1_THREADS) void sir_rows_kernel(uint8_t *__restr
                                              min(l_segment, m_segment + mine.lo), r);
 #pragma unroll
         for (int i = 0; i < SIR_LEAF; i++) w[i / 4] |= (((out >> i) & 1u) * par.value) << (8 * (i % 4));
-        sir1_store<ALIGNED>(line + col0, valid, w);
+        ksp_run_store_bytes(line + col0, valid, ALIGNED, ksp_run_bytes{w[0], w[1], w[2], w[3]});
         r_end = max(r_end, m_segment + all.hi);
         m_end = m_segment;
     }

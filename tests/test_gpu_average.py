@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 # 1024 baselines and a workgroup 4096.
 RUN = 16
 WORKGROUP_COLS = 256 * RUN
-BASELINES = [1, 3, 4, 5, 15, 16, 17, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025,
+BASELINES = [1, 3, 4, 5, 15, 16, 17, 33, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025,
              WORKGROUP_COLS - 1, WORKGROUP_COLS, WORKGROUP_COLS + 1]  # fmt: skip
 CHANNELS = [1, 2, 7, 8]
 N_DUMPS = 4
@@ -256,7 +256,7 @@ def test_tall(context, command_queue):
 @pytest.mark.parametrize("mode", ["NONE", "CHANNEL", "FULL"])
 @pytest.mark.parametrize("use_weights", [True, False])
 def test_options(use_weights, mode, context, command_queue):
-    for channels, baselines in [(7, 65), (8, 1025), (2, 16)]:
+    for channels, baselines in [(7, 65), (8, 1025), (2, 16), (1, 1), (5, 15), (2, 17), (3, 33)]:
         check_shape(context, command_queue, channels, baselines, seed=baselines, mode=mode,
                     use_weights=use_weights)  # fmt: skip
 
@@ -269,7 +269,7 @@ def test_padding(channels, baselines, pad, mode, context, command_queue):
     check_shape(context, command_queue, channels, baselines, seed=pad, mode=mode, pad=pad)
 
 
-@pytest.mark.parametrize("baselines", [5, 16, 257, 1040])
+@pytest.mark.parametrize("baselines", [1, 5, 15, 16, 17, 33, 257, 1040])
 def test_clear(baselines, context, command_queue):
     channels = 8
     rs = np.random.RandomState(baselines)
@@ -290,10 +290,23 @@ def test_clear(baselines, context, command_queue):
 def test_raw_abi_unaligned(mode, offset, context, command_queue):
     """Sub-views: pointers `offset` elements into their allocations, odd strides, a stride of
     its own per array."""
+    check_raw_abi(mode, offset, 37, context, command_queue)
+
+
+@pytest.mark.parametrize("baselines", [1, 15, 16, 17, 33])
+@pytest.mark.parametrize("mode", ["NONE", "CHANNEL", "FULL"])
+def test_raw_abi_unaligned_ragged(mode, baselines, context, command_queue):
+    """The same one element into the allocations (4 bytes for the weights, 1 for the flags),
+    at the widths around a run of 16: no run, a run short of one baseline, a whole run, runs
+    followed by one baseline."""
+    check_raw_abi(mode, 1, baselines, context, command_queue)
+
+
+def check_raw_abi(mode, offset, baselines, context, command_queue):
     from katsdpsigproc_amd import _lib
 
     queue = command_queue
-    channels, baselines, cf = 6, 37, 3
+    channels, cf = 6, 3
     dumps = make_dumps(np.random.RandomState(offset), channels, baselines, True, mode)
     strides = {"vis": 41, "flags": 39, "weights": 43, "mask": 45, "acc_vis": 37,
                "acc_weights": 47, "acc_flags": 49, "out_vis": 51, "out_weights": 37,

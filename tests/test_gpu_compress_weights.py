@@ -22,7 +22,7 @@ MEDIUM_MAX = 16384
 RESIDENT_MAX = 32768
 PATH_LIMITS = [WAVE_MAX, SMALL_MAX, MEDIUM_MAX, RESIDENT_MAX]
 BASELINES = sorted(
-    {1, 3, 15, 16, 17, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097}
+    {1, 3, 15, 16, 17, 33, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097}
     | {limit + d for limit in PATH_LIMITS for d in (-1, 0, 1)})  # fmt: skip
 CHANNELS = [1, 2, 7, 8]
 RUN = 16  # baselines of a 16-byte store
@@ -269,7 +269,8 @@ def aligned_strides(baselines):
     return -(-baselines // 4) * 4 + 4, -(-baselines // 16) * 16 + 16
 
 
-@pytest.mark.parametrize("channels, baselines", [(6, 37), (3, SMALL_MAX + 3), (2, RESIDENT_MAX + 232)])
+@pytest.mark.parametrize("channels, baselines", [(6, 37), (3, SMALL_MAX + 3), (2, RESIDENT_MAX + 232),
+                                                 (3, 1), (3, 15), (3, 16), (3, 17), (3, 33)])  # fmt: skip
 @pytest.mark.parametrize("offset, strides", [(1, odd_strides), (4, odd_strides), (12, odd_strides),
                                              (16, aligned_strides), (4, aligned_strides)])  # fmt: skip
 def test_raw_abi_subviews(offset, strides, channels, baselines, context, command_queue):

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 # wavefront spans 1024 baselines and a workgroup 4096; 1 and 7 channels end in a partial group of
 # rows either way, 2 with weights.
 WORKGROUP_COLS = 256 * 16
-BASELINES = [1, 3, 15, 16, 17, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025,
+BASELINES = [1, 3, 15, 16, 17, 33, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025,
              WORKGROUP_COLS - 1, WORKGROUP_COLS, WORKGROUP_COLS + 1]  # fmt: skip
 CHANNELS = [1, 2, 7, 8]
 LOST = -(2**31)
@@ -263,12 +263,30 @@ def test_raw_abi_subviews(offset, strides, variant, context, command_queue):
     per array. Odd strides take the element-wise path (offset 1 leaves vis_in on an odd
     multiple of 4 bytes); 16 elements and strides that keep the rows on 16 bytes take the
     16-byte path from the middle of an allocation."""
+    check_raw_abi(offset, strides, variant, 37, False, context, command_queue)
+
+
+@pytest.mark.parametrize("variant", [(False, False), (True, True)])
+@pytest.mark.parametrize("baselines", [1, 15, 16, 17, 33])
+@pytest.mark.parametrize("offset, strides", [(1, ODD_STRIDES), (16, ALIGNED_STRIDES)])
+def test_raw_abi_subviews_ragged(offset, strides, baselines, variant, context, command_queue):
+    """The same at the widths around a run of 16 (no run, a run short of one baseline, a whole
+    run, runs followed by one baseline), 4 bytes off and aligned, with indices outside the
+    input in the last baseline: the last element of a ragged run that is there. (What makes
+    that safe to run is said in front of test_invalid_indices.)"""
+    check_raw_abi(offset, strides, variant, baselines, True, context, command_queue)
+
+
+def check_raw_abi(offset, strides, variant, baselines, invalid_last, context, command_queue):
     from katsdpsigproc_amd import _lib
 
     queue = command_queue
-    channels, baselines, in_baselines = 6, 37, 21
+    channels, in_baselines = 6, 21
     use_mask, use_weights = variant
-    case = make_case(offset, channels, baselines, in_baselines, "permutation")
+    case = list(make_case(offset, channels, baselines, in_baselines, "permutation"))
+    if invalid_last:
+        case[1][-1] = in_baselines
+        case[3][-1] = [-1, 2**31 - 1]
     vis_in, source, channel_flags, auto_source = case
     # vis_in as rows of int32: a pair stride of n is a row stride of 2 n words
     d_in = flat_device_array(context, queue, np.int32, vis_in.reshape(channels, -1),
@@ -436,6 +454,7 @@ def test_invalid_indices(variant, context, command_queue):
         source, auto_source = case[1].copy(), case[3].copy()
         hit = rs.random_sample(baselines) < 0.3
         hit[: len(invalid)] = True
+        hit[-1] = True  # the last element of the row's last run, ragged or not
         source[hit] = invalid[np.arange(np.count_nonzero(hit)) % len(invalid)]
         hit = rs.random_sample((baselines, 2)) < 0.3
         hit[-1:] = True
