@@ -532,6 +532,46 @@ int ksp_range_percentiles(int device, void *stream, const void *in, const unsign
                           int out_stride, int counts_stride, int range_flags_stride,
                           const int *ranges, int n_ranges, int is_amplitude, int mask);
 
+/* band_average: per baseline and per series of channel weights (1..8 series), the weighted
+ * mean of the visibility and of its amplitude over the channels whose samples are neither NaN
+ * nor flagged under a mask, the weight sum, the number of samples kept and the OR of the flags
+ * of the series' channels; every sample is read once for all series (no reference
+ * counterpart; bit for bit what rfi/host.py BandAverageHost computes).
+ * data: complex64 [channels][data_stride], flags: uint8 [channels][flags_stride], of which
+ * `baselines` per row are data; channel_weights: float32 [n_series][channel_weights_stride],
+ * of which `channels` per row are data. mean: complex64 [n_series][mean_stride];
+ * mean_amplitude, weight_sums: float32, counts: uint32, series_flags: uint8, each
+ * [n_series][its stride], of which `baselines` per row are data. Strides in elements.
+ * For series k and baseline b, every step one float32 operation, rounded once (a multiply,
+ * then an add: never an fma), with w = channel_weights[k][c]:
+ *   in_k = w > 0 (a zero, negative or NaN weight leaves channel c out of series k);
+ *   kept = in_k and neither part of data[c][b] is NaN and (flags[c][b] & mask) == 0;
+ *   a = numpy's |data[c][b]|;
+ *   per block j of 128 consecutive channels (the last may be short), from +0.0, over the kept
+ *   c in ascending order: p_re += w * re, p_im += w * im, p_a += w * a, p_w += w;
+ *   S_re, S_im, S_a, S_w = the block partials added in ascending j from +0.0;
+ *   counts[k][b] = number of kept samples; series_flags[k][b] = OR of flags[c][b] over ALL c
+ *   with in_k; weight_sums[k][b] = S_w; mean[k][b] = S_w > 0 ? (S_re / S_w, S_im / S_w) : 0;
+ *   mean_amplitude[k][b] = S_w > 0 ? S_a / S_w : 0.
+ * flags and series_flags are both NULL (then mask must be 0 and their strides are ignored) or
+ * both given; mask is 0..255; channels is 1..262144, baselines at least 1. work_area is
+ * device memory of at least ksp_band_average_work_bytes(channels, baselines, n_series) =
+ * ceil(channels / 128) * n_series * 5 * baselines * 4 bytes (0 for sizes outside the limits),
+ * 4-byte aligned; it need not be cleared and holds nothing of use after the call; work_bytes
+ * is its size. Two kernel launches (block partials, then their ordered sum), no atomics.
+ * A sample is one 8-byte load and a flag one byte, whatever the alignment of the rows beyond
+ * that of their types. Elements beyond `baselines` of a row are never read or written. Every argument is checked
+ * before any device call. */
+size_t ksp_band_average_work_bytes(int channels, int baselines, int n_series);
+int ksp_band_average(int device, void *stream, const void *data, const unsigned char *flags,
+                     const float *channel_weights, void *mean, float *mean_amplitude,
+                     float *weight_sums, unsigned *counts, unsigned char *series_flags,
+                     void *work_area, size_t work_bytes, int channels, int baselines,
+                     int n_series, int data_stride, int flags_stride,
+                     int channel_weights_stride, int mean_stride, int mean_amplitude_stride,
+                     int weight_sums_stride, int counts_stride, int series_flags_stride,
+                     int mask);
+
 /* ---- masked_gaussian_filter (reference rfi/twodflag.py:254-400) ----
  * Images [images][rows][cols] of float32 (itemsize 4) or float64 (itemsize 8); data, flags
  * (uint8, non-zero = flagged) and out share image_stride and row_stride, in elements

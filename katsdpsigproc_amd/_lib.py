@@ -188,6 +188,11 @@ SIGNATURES = {
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
         c_int, c_int, c_int, c_int, POINTER(c_int), c_int, c_int, c_int,
     ],
+    "ksp_band_average": [
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+        c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+        c_int, c_int, c_int, c_int,
+    ],
     "ksp_launch_function": [
         c_int, c_void_p, c_void_p, POINTER(ctypes.c_uint), POINTER(ctypes.c_uint), ctypes.c_uint,
         POINTER(c_void_p),
@@ -197,6 +202,7 @@ SIGNATURES = {
 _OTHER = {
     "ksp_abi_version": ([], c_int),
     "ksp_last_error": ([], c_char_p),
+    "ksp_band_average_work_bytes": ([c_int, c_int, c_int], c_size_t),
 }
 
 #: functions whose int return value is a result, not an error code

@@ -727,6 +727,134 @@ class RangePercentilesHost:
         return percentiles, counts, range_flags
 
 
+class BandAverageHost:
+    """The other signal-display product of a dump, the "time series": for every baseline and
+    each of up to :attr:`MAX_SERIES` series of channel weights (a sub-band each, say), the
+    weighted mean of the visibility and of its amplitude over the channels that carry data,
+    the weight sum, how many samples were kept and the OR of the series' flags. No reference
+    counterpart; this class is the definition that the device operation
+    (:class:`.ingest.BandAverageTemplate`) matches bit for bit. For series ``k`` and baseline
+    ``b``, every step one float32 operation, rounded once, in this order::
+
+        w      = channel_weights[k, c]
+        in_k   = w > 0             (a zero, negative or NaN weight leaves channel c out of series k)
+        kept   = in_k and not isnan(re) and not isnan(im) and (flags[c, b] & mask) == 0
+                                   (no flags: no last term)
+        a      = numpy.abs(data[c, b])
+
+        for each block j of BLOCK consecutive channels (the last may be short), from +0.0:
+            for c ascending in the block, if kept:
+                p_re += w * re;  p_im += w * im;  p_a += w * a;  p_w += w
+                (a multiply, then an add: never an fma)
+        S_re, S_im, S_a, S_w = the block partials added in ascending j, from +0.0
+
+        counts[k, b]         = number of kept samples
+        series_flags[k, b]   = OR of flags[c, b] over ALL c with in_k, kept or not
+        weight_sums[k, b]    = S_w
+        mean[k, b]           = (S_re / S_w, S_im / S_w) if S_w > 0 else (0, 0)
+        mean_amplitude[k, b] = S_a / S_w if S_w > 0 else 0
+
+    Infinities and denormals go through as IEEE arithmetic gives them; a NaN sum makes
+    ``S_w > 0`` false only if it is the weight sum. A sample that is not kept adds nothing
+    (which, as every sum starts at +0.0, is the same as adding +0.0). Where a result is NaN
+    (``inf - inf``, ``inf / inf``) it is NaN on the device too; its sign and payload are the
+    processor's.
+
+    Why samples are left out: as for :class:`RangePercentilesHost`; and once they are, the
+    kept set differs from baseline to baseline, so the normaliser has to come from the same
+    pass. Why blocks: the device splits the reduction over channels to fill the chip, so the
+    order of the sums has to be fixed here and not by a launch geometry. :attr:`BLOCK` is
+    part of the arithmetic, not a tuning value.
+
+    Parameters
+    ----------
+    mask
+        0..255: a sample with ``flags & mask != 0`` is left out; 0 leaves out NaN alone
+        (:func:`check_mask_byte`)
+    """
+
+    BLOCK = 128
+    MAX_SERIES = 8
+    MAX_CHANNELS = 262144
+
+    def __init__(self, mask: int = 0) -> None:
+        self.mask = check_mask_byte("mask", mask)
+
+    def __call__(self, data: np.ndarray, channel_weights: np.ndarray,
+                 flags: Optional[np.ndarray] = None):  # fmt: skip
+        """``(mean, mean_amplitude, weight_sums, counts, series_flags)``: complex64, float32,
+        float32, uint32 and uint8 -- ``None`` without `flags` --, each (n_series, baselines),
+        for complex64 `data` (channels, baselines), both at least 1 and channels at most
+        262144, float32 `channel_weights` (n_series, channels) with 1 to 8 series, and
+        optional uint8 `flags` of `data`'s shape. ``TypeError`` for a non-zero mask without
+        `flags`; ``ValueError``, naming the argument, for a wrong dtype, rank or shape."""
+        data = _check_array("data", data, np.complex64, "(channels <= 262144, baselines)",
+                            lambda s: len(s) == 2 and 1 <= s[0] <= self.MAX_CHANNELS and s[1] >= 1)  # fmt: skip
+        channels, baselines = data.shape
+        channel_weights = _check_array(
+            "channel_weights", channel_weights, np.float32, "(1..8 series, channels)",
+            lambda s: len(s) == 2 and 1 <= s[0] <= self.MAX_SERIES and s[1] == channels)  # fmt: skip
+        if flags is None:
+            if self.mask != 0:
+                raise TypeError(f"mask {self.mask:#x} was given but flags were not provided")
+        else:
+            flags = _check_array("flags", flags, np.uint8, "(channels, baselines)",
+                                 lambda s: s == data.shape)  # fmt: skip
+        n_series = channel_weights.shape[0]
+        block = self.BLOCK
+        n_blocks = -(-channels // block)
+        padded = n_blocks * block
+        zero = np.float32(0)
+        with np.errstate(all="ignore"):
+            amplitude = np.abs(data)
+        assert amplitude.dtype == np.float32
+        ok = ~(np.isnan(data.real) | np.isnan(data.imag))
+        if flags is not None:
+            ok &= (flags & np.uint8(self.mask)) == 0
+
+        def blocks(values, fill):
+            """(channels, ...) as (n_blocks, BLOCK, ...), the short last block filled up."""
+            out = np.full((padded,) + values.shape[1:], fill, values.dtype)
+            out[:channels] = values
+            return out.reshape((n_blocks, block) + values.shape[1:])
+
+        parts = [blocks(np.ascontiguousarray(v), zero) for v in (data.real, data.imag, amplitude)]
+        ok_blocks = blocks(ok, False)
+        sums = np.zeros((4, n_series, baselines), np.float32)
+        counts = np.zeros((n_series, baselines), np.uint32)
+        series_flags = None if flags is None else np.zeros((n_series, baselines), np.uint8)
+        for k in range(n_series):
+            with np.errstate(invalid="ignore"):
+                in_k = channel_weights[k] > 0
+            w_blocks = blocks(np.where(in_k, channel_weights[k], zero), zero)
+            in_blocks = blocks(in_k, False)
+            partial = np.zeros((4, n_blocks, baselines), np.float32)
+            for i in range(min(block, channels)):  # the position inside a block, all blocks at once
+                kept = ok_blocks[:, i] & in_blocks[:, i, np.newaxis]
+                w = w_blocks[:, i, np.newaxis]
+                with np.errstate(all="ignore"):
+                    for t in range(3):
+                        partial[t] += np.where(kept, w * parts[t][:, i], zero)
+                    partial[3] += np.where(kept, w, zero)
+                counts[k] += kept.sum(axis=0, dtype=np.uint32)
+            with np.errstate(all="ignore"):
+                for j in range(n_blocks):
+                    sums[:, k] += partial[:, j]
+            if flags is not None and in_k.any():
+                series_flags[k] = np.bitwise_or.reduce(flags[in_k], axis=0)
+        s_w = sums[3]
+        with np.errstate(invalid="ignore"):
+            some = s_w > 0
+        divisor = np.where(some, s_w, np.float32(1))  # (no division where there is no result)
+        with np.errstate(all="ignore"):
+            mean = np.zeros((n_series, baselines), np.complex64)
+            mean.real[...] = np.where(some, sums[0] / divisor, zero)
+            mean.imag[...] = np.where(some, sums[1] / divisor, zero)
+            mean_amplitude = np.where(some, sums[2] / divisor, zero)
+        assert partial.dtype == np.float32 and mean_amplitude.dtype == np.float32
+        return mean, mean_amplitude, s_w.copy(), counts, series_flags
+
+
 class FlaggerHost(AbstractFlaggerHost):
     """background -> noise estimate -> threshold (reference rfi/host.py:257-273)."""
 

@@ -6,8 +6,11 @@ matches it bit for bit. And the step behind it: the float32 ``weights`` that
 one launch and bit for bit what :class:`.host.CompressWeightsHost` defines. And the step that
 closes it: the percentiles of the averaged amplitudes over ranges of baselines, flagged and NaN
 samples left out, with a count and the OR of the flags per range and channel: all ranges in one
-launch, bit for bit what :class:`.host.RangePercentilesHost` defines. The classes follow
-DESIGN.md, "Adding an operation".
+launch, bit for bit what :class:`.host.RangePercentilesHost` defines. And its companion: per
+baseline and for up to eight series of channel weights, the weighted means of the visibility and
+of its amplitude over the channels that carry data, with the weight sum, a count and the OR of
+the flags, every sample read once, bit for bit what :class:`.host.BandAverageHost` defines. The
+classes follow DESIGN.md, "Adding an operation".
 """
 
 import ctypes
@@ -407,3 +410,161 @@ class RangePercentilesHostFromDevice:
         outputs = ["percentiles", "counts"] + (["range_flags"] if template.use_flags else [])
         out = _native_op.run_once(fn, self.command_queue, {"data": data, "flags": flags}, outputs)
         return out[0], out[1], (out[2] if template.use_flags else None)
+
+
+class BandAverageTemplate(_native_op.NativeTemplate):
+    """The other display product of the ``vis`` and ``flags`` that :class:`.device.Finalise`
+    (or the flagger) leaves, the "time series": for every baseline and each of up to 8 series
+    of channel weights, the weighted mean of the visibility and of its amplitude over the
+    channels whose samples are neither NaN nor flagged under `mask`, the weight sum, the number
+    of samples kept and the OR of the flags of the series' channels. Every sample is read from
+    memory once, however many series there are; see :class:`host.BandAverageHost` for every
+    step.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernels
+    use_flags
+        ``True``: there are a `flags` and a `series_flags` slot
+    mask
+        As for :class:`host.BandAverageHost` (same errors); ``ValueError`` if it is not 0 and
+        `use_flags` is false
+    tuning
+        The launcher picks its launch geometry from the shape, and the block of the sums is
+        part of the definition: nothing to tune, any key is a ``ValueError``
+        (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.BandAverageHost
+    KERNEL = "ksp_band_average"
+
+    def __init__(self, context: AbstractContext, use_flags: bool = True, mask: int = 0,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        self.use_flags = bool(use_flags)
+        self.mask = host.check_mask_byte("mask", mask)
+        if self.mask != 0 and not self.use_flags:
+            raise ValueError(f"mask {self.mask:#x} needs use_flags")
+        self._setup(context, tuning)
+
+
+class BandAverage(_native_op.NativeOperation):
+    """Concrete :class:`BandAverageTemplate` (``ValueError`` unless `channels` is 1..262144,
+    `baselines` at least 1 and `n_series` 1..8).
+
+    .. rubric:: Slots
+
+    **data** : channels x baselines, complex64
+    **flags** : channels x baselines, uint8 (only with ``use_flags``)
+    **channel_weights** : n_series x channels, float32
+    **mean** : n_series x baselines, complex64
+    **mean_amplitude** : n_series x baselines, float32
+    **weight_sums** : n_series x baselines, float32
+    **counts** : n_series x baselines, uint32
+    **series_flags** : n_series x baselines, uint8 (only with ``use_flags``)
+    **work_area** : :meth:`work_bytes` scratch bytes for the partial sums of the blocks of
+    channels; exposed so that several operations that do not run at once can share one
+    allocation (it need not be cleared)
+
+    Every padded dimension is an object of its own, so ``data`` and ``flags`` can be
+    compounded with :class:`.device.Finalise`'s ``vis`` and ``flags`` (or the flagger's) and
+    take their padding.
+    """
+
+    def __init__(self, template: BandAverageTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int, n_series: int = 1,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        if not 1 <= channels <= host.BandAverageHost.MAX_CHANNELS or baselines < 1:
+            raise ValueError("channels must be 1..262144 and baselines at least 1")
+        if not 1 <= n_series <= host.BandAverageHost.MAX_SERIES:
+            raise ValueError(f"n_series must be 1..{host.BandAverageHost.MAX_SERIES}")
+        self.n_series = n_series
+
+        def series(dtype) -> accel.IOSlot:
+            return accel.IOSlot(
+                (accel.Dimension(n_series, exact=True), accel.Dimension(baselines)), dtype)  # fmt: skip
+
+        self.slots["data"] = accel.IOSlot((channels, accel.Dimension(baselines)), np.complex64)
+        if template.use_flags:
+            self.slots["flags"] = accel.IOSlot((channels, accel.Dimension(baselines)), np.uint8)
+        self.slots["channel_weights"] = accel.IOSlot(
+            (accel.Dimension(n_series, exact=True), accel.Dimension(channels)), np.float32)  # fmt: skip
+        self.slots["mean"] = series(np.complex64)
+        self.slots["mean_amplitude"] = series(np.float32)
+        self.slots["weight_sums"] = series(np.float32)
+        self.slots["counts"] = series(np.uint32)
+        if template.use_flags:
+            self.slots["series_flags"] = series(np.uint8)
+        self.slots["work_area"] = accel.IOSlot(
+            (accel.Dimension(self.work_bytes(channels, baselines, n_series), exact=True),), np.uint8)  # fmt: skip
+
+    @staticmethod
+    def work_bytes(channels: int, baselines: int, n_series: int) -> int:
+        """What ``ksp_band_average_work_bytes`` returns: five 4-byte words per block of
+        channels, series and baseline."""
+        n_blocks = -(-channels // host.BandAverageHost.BLOCK)
+        return n_blocks * n_series * 5 * baselines * 4
+
+    def _run(self) -> None:
+        template = self.template
+        names = ("data", "channel_weights", "mean", "mean_amplitude", "weight_sums", "counts")
+        data, weights, mean, amplitude, sums, counts = (self.buffer(name) for name in names)
+        flags = self.buffer("flags") if template.use_flags else None
+        series_flags = self.buffer("series_flags") if template.use_flags else None
+        work = self.buffer("work_area")
+        self._launch(
+            data.buffer,
+            flags.buffer if flags is not None else None,
+            weights.buffer,
+            mean.buffer,
+            amplitude.buffer,
+            sums.buffer,
+            counts.buffer,
+            series_flags.buffer if series_flags is not None else None,
+            work.buffer,
+            np.uint64(work.shape[0]),
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(self.n_series),
+            np.int32(data.padded_shape[1]),
+            np.int32(flags.padded_shape[1] if flags is not None else 0),
+            np.int32(weights.padded_shape[1]),
+            np.int32(mean.padded_shape[1]),
+            np.int32(amplitude.padded_shape[1]),
+            np.int32(sums.padded_shape[1]),
+            np.int32(counts.padded_shape[1]),
+            np.int32(series_flags.padded_shape[1] if series_flags is not None else 0),
+            np.int32(template.mask),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        template = self.template
+        return self._parameters(
+            use_flags=template.use_flags, mask=template.mask, n_series=self.n_series)  # fmt: skip
+
+
+BandAverageTemplate.operation_class = BandAverage
+
+
+class BandAverageHostFromDevice:
+    """Make a :class:`BandAverageTemplate` callable like :class:`host.BandAverageHost`:
+    ``(data, channel_weights, flags=None)`` in, ``(mean, mean_amplitude, weight_sums, counts,
+    series_flags or None)`` out; allocates on every call. ``TypeError`` unless `flags` is
+    given exactly when the template has ``use_flags``."""
+
+    def __init__(self, template: BandAverageTemplate, command_queue: AbstractCommandQueue) -> None:
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, data: np.ndarray, channel_weights: np.ndarray,
+                 flags: Optional[np.ndarray] = None):  # fmt: skip
+        template = self.template
+        _native_op.check_optional(flags, template.use_flags, "flags")
+        channels, baselines = data.shape
+        fn = template.instantiate(self.command_queue, channels, baselines, channel_weights.shape[0])
+        inputs = {"data": data, "channel_weights": channel_weights, "flags": flags}
+        outputs = ["mean", "mean_amplitude", "weight_sums", "counts"] + (
+            ["series_flags"] if template.use_flags else [])  # fmt: skip
+        out = _native_op.run_once(fn, self.command_queue, inputs, outputs)
+        return out[0], out[1], out[2], out[3], (out[4] if template.use_flags else None)
