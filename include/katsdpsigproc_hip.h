@@ -478,6 +478,32 @@ int ksp_prepare(int device, void *stream, const int32_t *vis_in, const int32_t *
                 int baselines, int vis_in_stride, int vis_stride, int input_flags_stride,
                 int weights_stride, float scale, float weight_scale, int lost_flag);
 
+/* prepare with flags per baseline: ksp_prepare and two more sources of input_flags, in the
+ * same launch (bit for bit what rfi/host.py PrepareHost computes with mask_index and
+ * baseline_flags). Everything said of ksp_prepare holds; in addition, for channel c and output
+ * baseline j:
+ *   cf = mask_classes == 0 ? (channel_flags ? channel_flags[c] : 0)
+ *      : mask_index[j] < mask_classes ? channel_flags[mask_index[j]][c] : 0;
+ *   input_flags = cf | (baseline_flags ? baseline_flags[j] : 0) | (lost ? lost_flag : 0).
+ * mask_classes is 0 .. 8. With 0, mask_index is NULL, channel_flags (may be NULL) is one row
+ * of uint8 [channels] and channel_flags_stride is ignored: with baseline_flags NULL as well
+ * this is ksp_prepare. With 1 .. 8, channel_flags is uint8 [mask_classes][channel_flags_stride]
+ * (a stride of at least channels, in elements) and must be given, as must mask_index, uint8
+ * [baselines]: the class of static mask of every output baseline. Any uint8 is allowed in it:
+ * a value of mask_classes or more (255, say) means "no static mask for this baseline" and is
+ * never used to form an address. baseline_flags (uint8 [baselines], may be NULL) is ORed
+ * into every sample of its baseline; vis and weights do not depend on it. Elements between
+ * channels and channel_flags_stride are never read. The 16-byte paths need mask_index and
+ * baseline_flags, where given, to be multiples of 16 bytes as well. Every argument is checked
+ * before any device call. */
+int ksp_prepare_flags(int device, void *stream, const int32_t *vis_in, const int32_t *source,
+                      const int32_t *auto_source, const uint8_t *channel_flags,
+                      const uint8_t *mask_index, const uint8_t *baseline_flags, void *vis,
+                      uint8_t *input_flags, float *weights, int channels, int in_baselines,
+                      int baselines, int mask_classes, int vis_in_stride,
+                      int channel_flags_stride, int vis_stride, int input_flags_stride,
+                      int weights_stride, float scale, float weight_scale, int lost_flag);
+
 /* compress_weights: float32 weights as one byte per sample and one float32 per channel, in
  * one launch (no reference counterpart; bit for bit what rfi/host.py CompressWeightsHost
  * computes; every float step is one float32 operation, rounded once).

@@ -8,7 +8,9 @@
 //     s = source[j];  valid = 0 <= s < in_baselines;  (re, im) = vis_in[c][valid ? s : 0]
 //     lost = !valid || re == -2^31
 //     vis = lost ? (0, 0) : (float(re) * scale, float(im) * scale)
-//     input_flags = channel_flags[c] | (lost ? lost_flag : 0)
+//     input_flags = cf | baseline_flags[j] | (lost ? lost_flag : 0)
+//       cf = channel_flags[c], or with mask_index (classes rows of channel_flags):
+//       k = mask_index[j];  cf = k < classes ? channel_flags[k][c] : 0
 //   with weights:
 //     power(k) = valid k && vis_in[c][k].re != -2^31 ? float(vis_in[c][k].re) * scale : 0
 //     pa, pb = power(auto_source[j][0]), power(auto_source[j][1]);  d = pa * pb
@@ -41,7 +43,20 @@
 // never read. (The run of run16.h, by hand: written on its helpers, with the arithmetic stated
 // once, the instances without weights were slower on the 16-byte path, profiles/run16.md.)
 //
-// Traffic per sample: 8 bytes gathered, 8 + 1 written, 4 more with weights.
+// Flags per baseline. mask_index and baseline_flags are one byte per output baseline, so a
+// lane keeps its run's 16 of each as four packed words (one 16-byte load each on the 16-byte
+// path, byte loads on the other) for all rows of its item, beside the source entries. The
+// classes' bytes of a row (channel_flags[k][row], k < classes <= 8) are the same for every
+// lane of the row: a lane loads them once per row into a pair of words, byte k for class k
+// and zero above `classes`, and picks the bytes of four samples at once with one v_perm_b32.
+// Its selectors are made once per run from the mask indices: the index itself below 8, and
+// 12, the selector of a zero byte, for everything else. So every uint8 in mask_index has a
+// result and none reaches an address. The element-wise path has no run to share a row's
+// words with: it loads the one byte it needs, from class 0 when the index is outside, and
+// drops it then.
+//
+// Traffic per sample: 8 bytes gathered, 8 + 1 written, 4 more with weights; the flags per
+// baseline are 2 bytes per 16 samples and group of rows.
 #include <limits.h>
 
 #include "launch.h"
@@ -49,6 +64,7 @@
 #define PREP_THREADS 256
 #define PREP_RUN 16
 #define PREP_ROWS(has_w) ((has_w) ? 4 : 2)
+#define PREP_MAX_CLASSES 8
 
 // `index` if it is inside 0 .. n - 1, else 0; `ok` says which
 __device__ __forceinline__ int prep_clamp(int index, int n, bool &ok)
@@ -71,17 +87,53 @@ __device__ __forceinline__ float prep_weight(float pa, float pb, float weight_sc
     return some ? q : 0.0f;
 }
 
+// channel_flags[k][row] of the classes k < `classes` (1 .. 8) as byte k of the eight bytes of
+// (lo, hi); the bytes at and above `classes` are zero. Eight loads whatever `classes` is,
+// those of the classes that are not there from class 0.
+__device__ __forceinline__ void prep_class_words(const uint8_t *__restrict__ channel_flags,
+                                                 long long stride, long long row, int classes,
+                                                 unsigned &lo, unsigned &hi)
+{
+    unsigned w[2] = {0, 0};
+#pragma unroll
+    for (int k = 0; k < PREP_MAX_CLASSES; k++) {
+        const bool there = k < classes;
+        const unsigned b = channel_flags[(there ? k : 0) * stride + row];
+        w[k / 4] |= (there ? b : 0u) << (8 * (k % 4));
+    }
+    lo = w[0];
+    hi = w[1];
+}
+
+// Four mask indices (the bytes of `index`) as the selectors of v_perm_b32 on such a pair: 0 .. 7
+// pick that byte of (lo, hi), 12 gives a zero byte and stands for every index of 8 or more.
+__device__ __forceinline__ unsigned prep_class_selectors(unsigned index)
+{
+    unsigned sel = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const unsigned m = (index >> (8 * k)) & 0xffu;
+        sel |= (m < (unsigned)PREP_MAX_CLASSES ? m : 12u) << (8 * k);
+    }
+    return sel;
+}
+
 // The instances with weights take 191 registers (two waves per SIMD): 48 indices, the 64 words
 // of a row's gathers and the 64-bit addresses of the loads in flight. Held to three waves they
 // were slower (profiles/prepare.md), held to four they spill: no occupancy bound.
-template <bool HAS_CF, bool HAS_W>
+// HAS_MI (classes of channel masks by mask_index; needs HAS_CF) and HAS_BF (baseline_flags)
+// are off in the four instances of ksp_prepare, which then do not touch the last four
+// arguments.
+template <bool HAS_CF, bool HAS_W, bool HAS_MI, bool HAS_BF>
 __global__ __launch_bounds__(PREP_THREADS) void prepare_kernel(
     const int *__restrict__ vis_in, const int *__restrict__ source,
     const int *__restrict__ auto_source, const uint8_t *__restrict__ channel_flags,
     float2 *__restrict__ vis, uint8_t *__restrict__ input_flags, float *__restrict__ weights,
     long long items, int runs_per_row, int channels, int in_baselines, int baselines,
     long long vis_in_stride, long long vis_stride, long long input_flags_stride,
-    long long weights_stride, float scale, float weight_scale, unsigned lost_flag, int aligned)
+    long long weights_stride, float scale, float weight_scale, unsigned lost_flag, int aligned,
+    const uint8_t *__restrict__ mask_index, const uint8_t *__restrict__ baseline_flags,
+    long long channel_flags_stride, int classes)
 {
     const long long item = (long long)blockIdx.x * PREP_THREADS + threadIdx.x;
     if (item >= items) return;
@@ -120,12 +172,22 @@ __global__ __launch_bounds__(PREP_THREADS) void prepare_kernel(
                 }
             }
         }
+        // and its mask indices (as selectors) and baseline flags, four bytes to a word
+        uint4 mi = make_uint4(0, 0, 0, 0), bf = make_uint4(0, 0, 0, 0);
+        if (HAS_MI) mi = *reinterpret_cast<const uint4 *>(mask_index + col0);
+        if (HAS_BF) bf = *reinterpret_cast<const uint4 *>(baseline_flags + col0);
+        const unsigned sel[4] = {prep_class_selectors(mi.x), prep_class_selectors(mi.y),
+                                 prep_class_selectors(mi.z), prep_class_selectors(mi.w)};
+        const unsigned bfw[4] = {bf.x, bf.y, bf.z, bf.w};
         for (int r = 0; r < rows; r++) {
             const long long row = row0 + r;
             const int *in = vis_in + 2 * row * vis_in_stride;
             float2 *v = vis + row * vis_stride + col0;
             uint8_t *fl = input_flags + row * input_flags_stride + col0;
-            const unsigned cf = HAS_CF ? channel_flags[row] : 0u;
+            const unsigned cf = HAS_CF && !HAS_MI ? channel_flags[row] : 0u;
+            unsigned cw_lo = 0, cw_hi = 0;
+            if (HAS_MI)
+                prep_class_words(channel_flags, channel_flags_stride, row, classes, cw_lo, cw_hi);
             int2 z[PREP_RUN];
 #pragma unroll
             for (int i = 0; i < PREP_RUN; i++) z[i] = reinterpret_cast<const int2 *>(in)[s[i]];
@@ -139,6 +201,8 @@ __global__ __launch_bounds__(PREP_THREADS) void prepare_kernel(
             for (int q = 0; q < 4; q++) {
                 float o[8];
                 fw[q] = cf * 0x01010101u;
+                if (HAS_BF) fw[q] |= bfw[q];
+                if (HAS_MI) fw[q] |= __builtin_amdgcn_perm(cw_hi, cw_lo, sel[q]);
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const int i = 4 * q + k;
@@ -176,6 +240,11 @@ __global__ __launch_bounds__(PREP_THREADS) void prepare_kernel(
                 ia = prep_clamp(auto_source[2 * (col0 + i)], in_baselines, ok_a);
                 ib = prep_clamp(auto_source[2 * (col0 + i) + 1], in_baselines, ok_b);
             }
+            // the class as an index that is inside, like source: class 0 when it is not
+            const unsigned m = HAS_MI ? mask_index[col0 + i] : 0u;
+            const bool ok_m = m < (unsigned)classes;
+            const long long cf0 = HAS_MI ? (ok_m ? m : 0u) * channel_flags_stride : 0;
+            const unsigned bfi = HAS_BF ? baseline_flags[col0 + i] : 0u;
             for (int r = 0; r < rows; r++) {
                 const long long row = row0 + r;
                 const int *in = vis_in + 2 * row * vis_in_stride;
@@ -185,9 +254,10 @@ __global__ __launch_bounds__(PREP_THREADS) void prepare_kernel(
                 z.x = lost ? 0.0f : __fmul_rn((float)re, scale);
                 z.y = lost ? 0.0f : __fmul_rn((float)im, scale);
                 vis[row * vis_stride + col0 + i] = z;
-                const unsigned cf = HAS_CF ? channel_flags[row] : 0u;
+                unsigned cf = HAS_CF ? channel_flags[cf0 + row] : 0u;
+                if (HAS_MI) cf = ok_m ? cf : 0u;
                 input_flags[row * input_flags_stride + col0 + i] =
-                    (uint8_t)(cf | (lost ? lost_flag : 0u));
+                    (uint8_t)(cf | bfi | (lost ? lost_flag : 0u));
                 if (HAS_W) {
                     const float pa = prep_power(in[2 * (long long)ia], ok_a, scale);
                     const float pb = prep_power(in[2 * (long long)ib], ok_b, scale);
@@ -200,12 +270,14 @@ __global__ __launch_bounds__(PREP_THREADS) void prepare_kernel(
 
 static bool prep_positive(float x) { return x > 0.0f && x <= 3.402823466e+38f; }
 
-extern "C" int ksp_prepare(int device, void *stream, const int32_t *vis_in, const int32_t *source,
-                           const int32_t *auto_source, const uint8_t *channel_flags, void *vis,
-                           uint8_t *input_flags, float *weights, int channels, int in_baselines,
-                           int baselines, int vis_in_stride, int vis_stride,
-                           int input_flags_stride, int weights_stride, float scale,
-                           float weight_scale, int lost_flag)
+extern "C" int ksp_prepare_flags(int device, void *stream, const int32_t *vis_in,
+                                 const int32_t *source, const int32_t *auto_source,
+                                 const uint8_t *channel_flags, const uint8_t *mask_index,
+                                 const uint8_t *baseline_flags, void *vis, uint8_t *input_flags,
+                                 float *weights, int channels, int in_baselines, int baselines,
+                                 int mask_classes, int vis_in_stride, int channel_flags_stride,
+                                 int vis_stride, int input_flags_stride, int weights_stride,
+                                 float scale, float weight_scale, int lost_flag)
 {
     KSP_REQUIRE(vis_in != nullptr, "vis_in is NULL");
     KSP_REQUIRE(source != nullptr, "source is NULL");
@@ -213,10 +285,18 @@ extern "C" int ksp_prepare(int device, void *stream, const int32_t *vis_in, cons
     KSP_REQUIRE(input_flags != nullptr, "input_flags is NULL");
     KSP_REQUIRE((auto_source == nullptr) == (weights == nullptr),
                 "auto_source and weights must both be given or both be NULL");
+    KSP_REQUIRE(mask_classes >= 0 && mask_classes <= PREP_MAX_CLASSES,
+                "mask_classes must be 0..8");
+    KSP_REQUIRE((mask_index == nullptr) == (mask_classes == 0),
+                "mask_index must be given exactly when mask_classes is not 0");
+    KSP_REQUIRE(mask_classes == 0 || channel_flags != nullptr,
+                "mask_classes of 1 or more need channel_flags");
     KSP_REQUIRE(channels >= 1, "channels must be at least 1");
     KSP_REQUIRE(in_baselines >= 1, "in_baselines must be at least 1");
     KSP_REQUIRE(baselines >= 1, "baselines must be at least 1");
     KSP_REQUIRE(vis_in_stride >= in_baselines, "vis_in_stride is smaller than in_baselines");
+    KSP_REQUIRE(mask_classes == 0 || channel_flags_stride >= channels,
+                "channel_flags_stride is smaller than channels");
     KSP_REQUIRE(vis_stride >= baselines, "vis_stride is smaller than baselines");
     KSP_REQUIRE(input_flags_stride >= baselines, "input_flags_stride is smaller than baselines");
     KSP_REQUIRE(weights == nullptr || weights_stride >= baselines,
@@ -234,6 +314,8 @@ extern "C" int ksp_prepare(int device, void *stream, const int32_t *vis_in, cons
     const int aligned =
         (uintptr_t)vis_in % 8 == 0 && ksp_rows_aligned(source, 0, 4) &&
         ksp_rows_aligned_if_given(auto_source, 0, 4) &&
+        ksp_rows_aligned_if_given(mask_index, 0, 1) &&
+        ksp_rows_aligned_if_given(baseline_flags, 0, 1) &&
         ksp_rows_aligned(vis, vis_stride, 8) &&
         ksp_rows_aligned(input_flags, input_flags_stride, 1) &&
         ksp_rows_aligned_if_given(weights, weights_stride, 4);
@@ -241,16 +323,34 @@ extern "C" int ksp_prepare(int device, void *stream, const int32_t *vis_in, cons
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)groups);
-    ksp_dispatch_exact<0, 1, 2, 3>(
-        (channel_flags != nullptr ? 1 : 0) + (weights != nullptr ? 2 : 0), [&](auto V) {
-            hipLaunchKernelGGL((prepare_kernel<(V() & 1) != 0, (V() & 2) != 0>), grid,
-                               dim3(PREP_THREADS), 0, s, (const int *)vis_in, (const int *)source,
-                               (const int *)auto_source, channel_flags, (float2 *)vis, input_flags,
-                               weights, items, runs_per_row, channels, in_baselines, baselines,
-                               (long long)vis_in_stride, (long long)vis_stride,
-                               (long long)input_flags_stride, (long long)weights_stride, scale,
-                               weight_scale, (unsigned)lost_flag, aligned);
-        });
+    // bit 0: channel mask, 1: weights, 2: classes of masks (only with bit 0), 3: baseline flags
+    const int variant = (channel_flags != nullptr ? 1 : 0) + (weights != nullptr ? 2 : 0) +
+                        (mask_index != nullptr ? 4 : 0) + (baseline_flags != nullptr ? 8 : 0);
+    ksp_dispatch_exact<0, 1, 2, 3, 5, 7, 8, 9, 10, 11, 13, 15>(variant, [&](auto V) {
+        hipLaunchKernelGGL(
+            (prepare_kernel<(V() & 1) != 0, (V() & 2) != 0, (V() & 4) != 0, (V() & 8) != 0>), grid,
+            dim3(PREP_THREADS), 0, s, (const int *)vis_in, (const int *)source,
+            (const int *)auto_source, channel_flags, (float2 *)vis, input_flags, weights, items,
+            runs_per_row, channels, in_baselines, baselines, (long long)vis_in_stride,
+            (long long)vis_stride, (long long)input_flags_stride, (long long)weights_stride, scale,
+            weight_scale, (unsigned)lost_flag, aligned, mask_index, baseline_flags,
+            (long long)channel_flags_stride, mask_classes);
+    });
     KSP_LAUNCH_CHECK();
     return 0;
+}
+
+// The four instances without classes and baseline flags, with the checks and results it had
+// before ksp_prepare_flags.
+extern "C" int ksp_prepare(int device, void *stream, const int32_t *vis_in, const int32_t *source,
+                           const int32_t *auto_source, const uint8_t *channel_flags, void *vis,
+                           uint8_t *input_flags, float *weights, int channels, int in_baselines,
+                           int baselines, int vis_in_stride, int vis_stride,
+                           int input_flags_stride, int weights_stride, float scale,
+                           float weight_scale, int lost_flag)
+{
+    return ksp_prepare_flags(device, stream, vis_in, source, auto_source, channel_flags, nullptr,
+                             nullptr, vis, input_flags, weights, channels, in_baselines, baselines,
+                             0, vis_in_stride, 0, vis_stride, input_flags_stride, weights_stride,
+                             scale, weight_scale, lost_flag);
 }

@@ -457,9 +457,21 @@ class PrepareHost:
         s    = source[j];  valid = 0 <= s < in_baselines
         lost = not valid or vis_in[c, s].re == -2**31
         vis  = lost ? 0 : (float32(re) * scale, float32(im) * scale)
-        input_flags = channel_flags[c] | (lost ? lost_flag : 0)
+        input_flags = cf | baseline_flags[j] | (lost ? lost_flag : 0)
 
-    and, with `auto_source` (the input baselines of the autocorrelations of the two inputs of
+    where ``cf`` is ``channel_flags[c]``, one static byte per channel for every baseline
+    alike, or, with `mask_index`, the byte of the baseline's class of static mask (a known-RFI
+    mask that applies to short baselines only, say)::
+
+        k  = mask_index[j]                                  (uint8; any value is allowed)
+        cf = k < classes ? channel_flags[k, c] : 0          (classes = len(channel_flags))
+
+    An index of ``classes`` or more (255, say) means "no static mask for this baseline".
+    ``baseline_flags[j]`` is ORed into every sample of baseline ``j`` (an antenna that is off
+    target flags every baseline it takes part in); ``vis`` and ``weights`` do not depend on
+    it, so :class:`AveragerHost` treats such a sample like any flagged one.
+
+    And, with `auto_source` (the input baselines of the autocorrelations of the two inputs of
     every output baseline)::
 
         power(k) = valid k and vis_in[c, k].re != -2**31 ? float32(vis_in[c, k].re) * scale : 0
@@ -479,6 +491,7 @@ class PrepareHost:
     """
 
     LOST = np.int32(-(2**31))
+    MAX_CLASSES = 8
 
     def __init__(self, scale: float = 1.0, lost_flag: int = 8, weight_scale: float = 1.0) -> None:
         self.scale = _check_positive_float32("scale", scale)
@@ -493,23 +506,40 @@ class PrepareHost:
 
     def __call__(self, vis_in: np.ndarray, source: np.ndarray,
                  channel_flags: Optional[np.ndarray] = None,
-                 auto_source: Optional[np.ndarray] = None):  # fmt: skip
+                 auto_source: Optional[np.ndarray] = None,
+                 baseline_flags: Optional[np.ndarray] = None,
+                 mask_index: Optional[np.ndarray] = None):  # fmt: skip
         """``(vis, input_flags, weights)`` for int32 `vis_in` (channels, in_baselines, 2),
-        int32 `source` (baselines,), optional uint8 `channel_flags` (channels,) and optional
-        int32 `auto_source` (baselines, 2); ``weights`` is ``None`` without `auto_source`.
-        ``ValueError``, naming the argument, for a wrong dtype, rank or shape."""
+        int32 `source` (baselines,), optional uint8 `channel_flags` (channels,), optional
+        int32 `auto_source` (baselines, 2), optional uint8 `baseline_flags` (baselines,) and
+        optional uint8 `mask_index` (baselines,), with which `channel_flags` is (classes,
+        channels), classes 1..:attr:`MAX_CLASSES`, and without which it is not; ``weights`` is
+        ``None`` without `auto_source`. ``ValueError``, naming the argument, for a wrong dtype,
+        rank or shape."""
         vis_in = _check_array("vis_in", vis_in, np.int32, "(channels, in_baselines, 2)",
                               lambda s: len(s) == 3 and s[0] >= 1 and s[1] >= 1 and s[2] == 2)  # fmt: skip
         channels = vis_in.shape[0]
         source = _check_array("source", source, np.int32, "(baselines,)",
                               lambda s: len(s) == 1 and s[0] >= 1)  # fmt: skip
         baselines = source.shape[0]
-        if channel_flags is not None:
+        if mask_index is not None:
+            mask_index = _check_array("mask_index", mask_index, np.uint8, "(baselines,)",
+                                      lambda s: s == (baselines,))  # fmt: skip
+            if channel_flags is None:
+                raise ValueError("mask_index needs channel_flags of shape (classes, channels)")
+            channel_flags = _check_array(
+                "channel_flags", channel_flags, np.uint8,
+                f"(classes, channels) with 1 to {self.MAX_CLASSES} classes",
+                lambda s: len(s) == 2 and 1 <= s[0] <= self.MAX_CLASSES and s[1] == channels)
+        elif channel_flags is not None:
             channel_flags = _check_array("channel_flags", channel_flags, np.uint8, "(channels,)",
                                          lambda s: s == (channels,))  # fmt: skip
         if auto_source is not None:
             auto_source = _check_array("auto_source", auto_source, np.int32, "(baselines, 2)",
                                        lambda s: s == (baselines, 2))  # fmt: skip
+        if baseline_flags is not None:
+            baseline_flags = _check_array("baseline_flags", baseline_flags, np.uint8,
+                                          "(baselines,)", lambda s: s == (baselines,))  # fmt: skip
         valid = (source >= 0) & (source < vis_in.shape[1])
         picked = vis_in[:, np.where(valid, source, 0)]
         lost = ~valid[np.newaxis, :] | (picked[..., 0] == self.LOST)
@@ -519,8 +549,14 @@ class PrepareHost:
         vis.real[...] = np.where(lost, np.float32(0), scaled[..., 0])
         vis.imag[...] = np.where(lost, np.float32(0), scaled[..., 1])
         input_flags = np.where(lost, np.uint8(self.lost_flag), np.uint8(0))
-        if channel_flags is not None:
+        if mask_index is not None:
+            known = mask_index < channel_flags.shape[0]
+            static = channel_flags[np.where(known, mask_index, 0)].T
+            input_flags = input_flags | np.where(known[np.newaxis, :], static, np.uint8(0))
+        elif channel_flags is not None:
             input_flags = input_flags | channel_flags[:, np.newaxis]
+        if baseline_flags is not None:
+            input_flags = input_flags | baseline_flags[np.newaxis, :]
         weights = None
         if auto_source is not None:
             with np.errstate(all="ignore"):

@@ -1,7 +1,8 @@
 """The step in front of the flagging chain: a correlator's integer dump, as it arrives, to the
 ``vis``, ``input_flags`` and ``weights`` that :mod:`.device` takes as inputs, in one kernel
 launch (no reference counterpart). :class:`.host.PrepareHost` is the definition; the kernel
-matches it bit for bit. And the step behind it: the float32 ``weights`` that
+matches it bit for bit, static channel masks chosen per baseline and flags per baseline
+included. And the step behind it: the float32 ``weights`` that
 :class:`.device.Finalise` leaves to one byte per sample and one float32 per channel, again in
 one launch and bit for bit what :class:`.host.CompressWeightsHost` defines. And the step that
 closes it: the percentiles of the averaged amplitudes over ranges of baselines, flagged and NaN
@@ -47,6 +48,14 @@ class PrepareTemplate(_native_op.NativeTemplate):
         every sample of its channel
     weights
         ``True``: there are an `auto_source` and a `weights` slot
+    mask_classes
+        0 .. 8 (``ValueError``). 1 or more: the `channel_flags` slot holds that many static
+        masks, one per row, and there is a `mask_index` slot that names the row of every
+        baseline (a value of `mask_classes` or more: none). Needs `channel_flags`
+        (``ValueError``).
+    baseline_flags
+        ``True``: there is a `baseline_flags` slot, one byte per baseline that is ORed into
+        every sample of its baseline
     tuning
         The kernel picks its launch geometry from the shape: nothing to tune, any key is a
         ``ValueError`` (:func:`.tune.fixed_geometry`).
@@ -54,9 +63,12 @@ class PrepareTemplate(_native_op.NativeTemplate):
 
     host_class = host.PrepareHost
     KERNEL = "ksp_prepare"
+    #: the launcher of a template with `mask_classes` or `baseline_flags`
+    FLAGS_KERNEL = "ksp_prepare_flags"
 
     def __init__(self, context: AbstractContext, scale: float = 1.0, lost_flag: int = 8,
                  channel_flags: bool = False, weights: bool = False, weight_scale: float = 1.0,
+                 mask_classes: int = 0, baseline_flags: bool = False,
                  tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
         checked = host.PrepareHost(scale, lost_flag, weight_scale)
         self.scale = checked.scale
@@ -64,7 +76,16 @@ class PrepareTemplate(_native_op.NativeTemplate):
         self.weight_scale = checked.weight_scale
         self.channel_flags = bool(channel_flags)
         self.weights = bool(weights)
+        self.mask_classes = int(mask_classes)
+        self.baseline_flags = bool(baseline_flags)
+        if not 0 <= self.mask_classes <= host.PrepareHost.MAX_CLASSES:
+            raise ValueError(f"mask_classes must be 0..{host.PrepareHost.MAX_CLASSES}")
+        if self.mask_classes >= 1 and not self.channel_flags:
+            raise ValueError("mask_classes of 1 or more need channel_flags")
         self._setup(context, tuning)
+        self.per_baseline = self.mask_classes >= 1 or self.baseline_flags
+        if self.per_baseline:
+            self.kernel = context.native_kernel(self.FLAGS_KERNEL)
 
 
 class Prepare(_native_op.NativeOperation):
@@ -76,7 +97,10 @@ class Prepare(_native_op.NativeOperation):
 
     **vis_in** : channels x in_baselines x 2, int32, (re, im)
     **source** : baselines, int32: the input baseline of every output baseline
-    **channel_flags** : channels, uint8 (only with ``channel_flags``)
+    **channel_flags** : channels, uint8 (only with ``channel_flags``); with ``mask_classes``
+    of 1 or more: mask_classes x channels
+    **mask_index** : baselines, uint8 (only with ``mask_classes`` of 1 or more)
+    **baseline_flags** : baselines, uint8 (only with ``baseline_flags``)
     **auto_source** : baselines x 2, int32: the input baselines of the two autocorrelations
     of every output baseline (only with ``weights``)
     **vis** : channels x baselines, complex64
@@ -106,8 +130,15 @@ class Prepare(_native_op.NativeOperation):
         self.slots["vis_in"] = accel.IOSlot(
             (channels, accel.Dimension(in_baselines), pair()), np.int32)  # fmt: skip
         self.slots["source"] = accel.IOSlot((accel.Dimension(baselines),), np.int32)
-        if template.channel_flags:
+        if template.mask_classes >= 1:
+            self.slots["channel_flags"] = accel.IOSlot(
+                (accel.Dimension(template.mask_classes, exact=True), accel.Dimension(channels)),
+                np.uint8)  # fmt: skip
+            self.slots["mask_index"] = accel.IOSlot((accel.Dimension(baselines),), np.uint8)
+        elif template.channel_flags:
             self.slots["channel_flags"] = accel.IOSlot((accel.Dimension(channels),), np.uint8)
+        if template.baseline_flags:
+            self.slots["baseline_flags"] = accel.IOSlot((accel.Dimension(baselines),), np.uint8)
         if template.weights:
             self.slots["auto_source"] = accel.IOSlot(
                 (accel.Dimension(baselines), pair()), np.int32)  # fmt: skip
@@ -123,6 +154,9 @@ class Prepare(_native_op.NativeOperation):
         auto_source = self.buffer("auto_source") if template.weights else None
         vis, input_flags = self.buffer("vis"), self.buffer("input_flags")
         weights = self.buffer("weights") if template.weights else None
+        if template.per_baseline:
+            self._run_flags(vis_in, source, channel_flags, auto_source, vis, input_flags, weights)
+            return
         self._launch(
             vis_in.buffer,
             source.buffer,
@@ -143,9 +177,41 @@ class Prepare(_native_op.NativeOperation):
             np.int32(template.lost_flag),
         )
 
+    def _run_flags(self, vis_in, source, channel_flags, auto_source, vis, input_flags,
+                   weights) -> None:  # fmt: skip
+        """Launch ``ksp_prepare_flags``: the arguments of ``ksp_prepare`` and `mask_index`,
+        `baseline_flags`, the number of classes and the row stride of `channel_flags`."""
+        template = self.template
+        classes = template.mask_classes
+        mask_index = self.buffer("mask_index") if classes >= 1 else None
+        baseline_flags = self.buffer("baseline_flags") if template.baseline_flags else None
+        self._launch(
+            vis_in.buffer,
+            source.buffer,
+            auto_source.buffer if auto_source is not None else None,
+            channel_flags.buffer if channel_flags is not None else None,
+            mask_index.buffer if mask_index is not None else None,
+            baseline_flags.buffer if baseline_flags is not None else None,
+            vis.buffer,
+            input_flags.buffer,
+            weights.buffer if weights is not None else None,
+            np.int32(self.channels),
+            np.int32(self.in_baselines),
+            np.int32(self.baselines),
+            np.int32(classes),
+            np.int32(vis_in.padded_shape[1]),
+            np.int32(channel_flags.padded_shape[1] if classes >= 1 else 0),
+            np.int32(vis.padded_shape[1]),
+            np.int32(input_flags.padded_shape[1]),
+            np.int32(weights.padded_shape[1] if weights is not None else 0),
+            np.float32(template.scale),
+            np.float32(template.weight_scale),
+            np.int32(template.lost_flag),
+        )
+
     def parameters(self) -> Mapping[str, Any]:
         template = self.template
-        return self._parameters(
+        own = dict(
             scale=float(template.scale),
             lost_flag=template.lost_flag,
             channel_flags=template.channel_flags,
@@ -153,6 +219,12 @@ class Prepare(_native_op.NativeOperation):
             weight_scale=float(template.weight_scale),
             in_baselines=self.in_baselines,
         )
+        # (only when they are on: without them this is the dict it always was)
+        if template.mask_classes >= 1:
+            own["mask_classes"] = template.mask_classes
+        if template.baseline_flags:
+            own["baseline_flags"] = True
+        return self._parameters(**own)
 
 
 PrepareTemplate.operation_class = Prepare
@@ -160,9 +232,11 @@ PrepareTemplate.operation_class = Prepare
 
 class PrepareHostFromDevice:
     """Make a :class:`PrepareTemplate` callable like :class:`host.PrepareHost`:
-    ``(vis_in, source, channel_flags=None, auto_source=None)`` in, ``(vis, input_flags,
-    weights or None)`` out; allocates on every call. ``TypeError`` unless `channel_flags` and
-    `auto_source` are given exactly when the template has them."""
+    ``(vis_in, source, channel_flags=None, auto_source=None, baseline_flags=None,
+    mask_index=None)`` in, ``(vis, input_flags, weights or None)`` out; allocates on every
+    call. ``TypeError`` unless each optional input is given exactly when the template has it
+    (`mask_index`: with ``mask_classes`` of 1 or more, and `channel_flags` then has that many
+    rows, ``ValueError`` otherwise)."""
 
     def __init__(self, template: PrepareTemplate, command_queue: AbstractCommandQueue) -> None:
         self.template = template
@@ -170,15 +244,23 @@ class PrepareHostFromDevice:
 
     def __call__(self, vis_in: np.ndarray, source: np.ndarray,
                  channel_flags: Optional[np.ndarray] = None,
-                 auto_source: Optional[np.ndarray] = None
+                 auto_source: Optional[np.ndarray] = None,
+                 baseline_flags: Optional[np.ndarray] = None,
+                 mask_index: Optional[np.ndarray] = None
                  ) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:  # fmt: skip
         template = self.template
         _native_op.check_optional(channel_flags, template.channel_flags, "channel_flags")
         _native_op.check_optional(auto_source, template.weights, "auto_source")
+        _native_op.check_optional(baseline_flags, template.baseline_flags, "baseline_flags")
+        _native_op.check_optional(mask_index, template.mask_classes >= 1, "mask_index")
+        if mask_index is not None and np.shape(channel_flags)[:-1] != (template.mask_classes,):
+            raise ValueError(f"channel_flags must have {template.mask_classes} rows, the "
+                             f"template's mask_classes, not shape {np.shape(channel_flags)}")
         channels, in_baselines = vis_in.shape[:2]
         fn = template.instantiate(self.command_queue, channels, source.shape[0], in_baselines)
         inputs = {"vis_in": vis_in, "source": source, "channel_flags": channel_flags,
-                  "auto_source": auto_source}  # fmt: skip
+                  "auto_source": auto_source, "baseline_flags": baseline_flags,
+                  "mask_index": mask_index}  # fmt: skip
         outputs = ["vis", "input_flags"] + (["weights"] if template.weights else [])
         out = _native_op.run_once(fn, self.command_queue, inputs, outputs)
         return out[0], out[1], (out[2] if template.weights else None)

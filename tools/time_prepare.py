@@ -28,6 +28,17 @@ Timed in alternation with the operation, in the same rounds:
   35 bytes per sample, all of them streamed, against the 17 (21 with weights) of this
   operation, 8 of which are gathered.
 
+And, on the same buffers, the instance with flags per baseline (two classes of static mask,
+the second for the first eighth of the baselines only, the last quarter with none, and
+``baseline_flags`` set on 3 % of the baselines; ``ksp_prepare_flags``) against
+
+* the option-free instance above: the cost of the feature;
+* what a caller does without it: the option-free instance followed by the torch composite
+  ``input_flags |= baseline_flags[None, :] | masks[index]`` (one gather, two ORs and a pass
+  over ``input_flags``; "no mask" is a row of zeros behind the classes).
+
+Both are checked bit for bit against ``rfi.host.PrepareHost`` on the sampled rows.
+
 Usage: ``python tools/time_prepare.py [--channels C] [--baselines B] [--rounds N] [--calls N]
 [--json OUT]`` (`baselines` a multiple of 4, at least 1024).
 """
@@ -51,6 +62,7 @@ LOST = -(2**31)
 SCALE, LOST_FLAG, WEIGHT_SCALE = 2.0**-8, 8, 2.0**24
 ANTENNAS = 128
 SAMPLED_ROWS = 8
+CLASSES, MASK_BITS, OFF_TARGET = 2, (0x20, 0x10), 0x40
 
 
 class _View:
@@ -144,6 +156,26 @@ def torch_prepare(t, source, auto_source, use_weights):
         t["weights"].copy_(torch.where(some, WEIGHT_SCALE / d, 0.0))
 
 
+def flag_inputs(channels, baselines):
+    """(masks, mask_index, baseline_flags) of the instance with flags per baseline."""
+    rs = np.random.RandomState(4)
+    masks = np.zeros((CLASSES, channels), np.uint8)
+    for k, bit in enumerate(MASK_BITS):
+        masks[k, rs.random_sample(channels) < 0.125] = bit
+    mask_index = np.zeros(baselines, np.uint8)
+    mask_index[: baselines // 8] = 1
+    mask_index[-(baselines // 4) :] = 255
+    baseline_flags = np.where(rs.random_sample(baselines) < 0.03, OFF_TARGET, 0).astype(np.uint8)
+    return masks, mask_index, baseline_flags
+
+
+def torch_flags(t, masks_t, index, baseline_flags):
+    """What a caller ORs into `input_flags` after the option-free operation. `masks_t` is
+    channels x (classes + 1), the last column zeros; `index` is clipped to it."""
+    static = masks_t.index_select(1, index)
+    t["input_flags"].bitwise_or_(static | baseline_flags.unsqueeze(0))
+
+
 def text(entry):
     return f"{entry['median_ms']:.3f} ms ({entry['min_ms']:.3f}..{entry['max_ms']:.3f})"
 
@@ -175,6 +207,18 @@ def main():
         op = ingest.PrepareTemplate(context, SCALE, LOST_FLAG, False, use_weights,
                                     WEIGHT_SCALE).instantiate(queue, channels, baselines)  # fmt: skip
         op.ensure_all_bound()
+        op_flags = ingest.PrepareTemplate(
+            context, SCALE, LOST_FLAG, True, use_weights, WEIGHT_SCALE, mask_classes=CLASSES,
+            baseline_flags=True).instantiate(queue, channels, baselines)  # fmt: skip
+        op_flags.bind(**{name: op.buffer(name) for name in op.slots})
+        op_flags.ensure_all_bound()
+        masks, mask_index, baseline_flags = flag_inputs(channels, baselines)
+        op_flags.buffer("channel_flags").set(queue, masks)
+        op_flags.buffer("mask_index").set(queue, mask_index)
+        op_flags.buffer("baseline_flags").set(queue, baseline_flags)
+        masks_t = torch.as_tensor(np.vstack([masks, np.zeros_like(masks[:1])]).T.copy(), device="cuda")
+        d_index = torch.as_tensor(np.minimum(mask_index, CLASSES).astype(np.int64), device="cuda")
+        d_baseline_flags = torch.as_tensor(baseline_flags, device="cuda")
         yardstick = device.AccumulateTemplate(context, use_weights=False).instantiate(
             queue, channels, baselines)  # fmt: skip
         yardstick.bind(vis=op.buffer("vis"), flags=op.buffer("input_flags"))
@@ -191,6 +235,8 @@ def main():
             if use_weights:
                 op.buffer("auto_source").set(queue, auto_source)
             want = reference(vis_in_host, source, None, auto_source if use_weights else None)
+            want_flags = reference(vis_in_host, source, masks[:, rows],
+                                   auto_source if use_weights else None, baseline_flags, mask_index)  # fmt: skip
             d_source = torch.as_tensor(source.astype(np.int64), device="cuda")
             d_auto = torch.as_tensor(auto_source.astype(np.int64), device="cuda")
             outputs = ["vis", "input_flags"] + (["weights"] if use_weights else [])
@@ -202,6 +248,15 @@ def main():
             def composite():
                 torch_prepare(t, d_source, d_auto, use_weights)
 
+            def today():
+                op()
+                torch_flags(t, masks_t, d_index, d_baseline_flags)
+
+            def check(expected):
+                queue.finish()
+                for which, w in zip(outputs, expected):
+                    np.testing.assert_array_equal(sampled(which).view(np.uint8), w.view(np.uint8))
+
             # the composite first, checked, then the operation (warm-up, and the call checked)
             composite()
             torch.cuda.synchronize()
@@ -212,16 +267,23 @@ def main():
                     np.testing.assert_array_equal(sampled(which).view(np.uint8), w.view(np.uint8))
             for which in outputs:
                 t[which].zero_()
+            op_flags()
+            check(want_flags)
+            assert (sampled("input_flags") & (OFF_TARGET | sum(MASK_BITS))).any()
+            today()
+            check(want_flags)
             op()
-            queue.finish()
-            for which, w in zip(outputs, want):
-                np.testing.assert_array_equal(sampled(which).view(np.uint8), w.view(np.uint8))
+            check(want)
             yardstick()
             queue.finish()
-            timed = time_rounds(queue, [op, composite, yardstick], args.rounds, args.calls)
+            timed = time_rounds(queue, [op, composite, yardstick, op_flags, today], args.rounds,
+                                args.calls)  # fmt: skip
             run = {"map": name, "weights": use_weights, "verified": True, "bytes": int(n_bytes),
                    "op": timed[0], "torch_composite": timed[1], "accumulate": timed[2],
-                   "accumulate_bytes": int(samples * 35)}  # fmt: skip
+                   "accumulate_bytes": int(samples * 35), "op_flags": timed[3],
+                   "op_then_torch_flags": timed[4],
+                   "flags_over_op": timed[3]["median_ms"] / timed[0]["median_ms"],
+                   "today_over_flags": timed[4]["median_ms"] / timed[3]["median_ms"]}  # fmt: skip
             run["op"]["bytes_per_s"] = n_bytes / (timed[0]["median_ms"] * 1e-3)
             run["accumulate"]["bytes_per_s"] = samples * 35 / (timed[2]["median_ms"] * 1e-3)
             run["torch_over_op"] = timed[1]["median_ms"] / timed[0]["median_ms"]
@@ -229,9 +291,12 @@ def main():
                   f"{run['op']['bytes_per_s'] / 1e12:.2f} TB/s; torch composite {text(timed[1])}, "
                   f"{run['torch_over_op']:.1f} x; Accumulate {text(timed[2])}, "
                   f"{run['accumulate']['bytes_per_s'] / 1e12:.2f} TB/s", flush=True)  # fmt: skip
+            print(f"      with {CLASSES} classes + baseline flags: op {text(timed[3])}, "
+                  f"{run['flags_over_op']:.3f} x the option-free op; option-free op + torch ORs "
+                  f"{text(timed[4])}, {run['today_over_flags']:.2f} x", flush=True)  # fmt: skip
             result["runs"].append(run)
             del d_source, d_auto
-        del op, yardstick, t
+        del op, op_flags, yardstick, t, masks_t, d_index, d_baseline_flags
         torch.cuda.empty_cache()
     if args.json:
         with open(args.json, "w") as f:
