@@ -415,13 +415,30 @@ int ksp_flag_count(int device, void *stream, const uint8_t *flags, uint32_t *row
  * if w < 2^-32 ("every contribution was flagged") re, im and w are multiplied by 2^64;
  * out_vis = w > 0 ? (re / w, im / w) : (0, 0) with two correctly rounded divisions;
  * out_weights = w; out_flags = fl if every contribution was flagged, else 0.
- * clear != 0: the accumulator elements that were read are set to zero in the same pass. */
+ * clear != 0: the accumulator elements that were read are set to zero in the same pass.
+ *
+ * ksp_average_accumulate_block adds n_dumps dumps (1..8) in one launch: for every sample
+ * the steps of ksp_average_accumulate on dump 0, then on dump 1, and so on, so the result is
+ * bit for bit that of n_dumps calls in that order, while the accumulators are read and
+ * written once. vis, flags, weights and input_flags are host arrays of n_dumps device
+ * pointers (read during the call); the dumps are read-only and may repeat. weights as a
+ * whole may be NULL, input_flags as a whole is NULL exactly when the mode is 0, and no entry
+ * of a list that is given may be NULL. One row stride per kind serves every dump. One
+ * pointer of one dump that is not 16-byte aligned sends the whole call down the element
+ * path. */
 int ksp_average_accumulate(int device, void *stream, const void *vis, const uint8_t *flags,
                            const float *weights, const uint8_t *input_flags,
                            int input_flags_mode, void *acc_vis, float *acc_weights,
                            uint8_t *acc_flags, int channels, int baselines, int vis_stride,
                            int flags_stride, int weights_stride, int input_flags_stride,
                            int acc_vis_stride, int acc_weights_stride, int acc_flags_stride);
+int ksp_average_accumulate_block(int device, void *stream, int n_dumps, const void *const *vis,
+                                 const uint8_t *const *flags, const float *const *weights,
+                                 const uint8_t *const *input_flags, int input_flags_mode,
+                                 void *acc_vis, float *acc_weights, uint8_t *acc_flags,
+                                 int channels, int baselines, int vis_stride, int flags_stride,
+                                 int weights_stride, int input_flags_stride, int acc_vis_stride,
+                                 int acc_weights_stride, int acc_flags_stride);
 int ksp_average_finalise(int device, void *stream, void *acc_vis, float *acc_weights,
                          uint8_t *acc_flags, void *out_vis, float *out_weights,
                          uint8_t *out_flags, int channels, int baselines, int channel_factor,

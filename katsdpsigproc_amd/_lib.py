@@ -172,6 +172,10 @@ SIGNATURES = {
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
         c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
     ],
+    "ksp_average_accumulate_block": [
+        c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+        c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+    ],
     "ksp_average_finalise": [
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
         c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

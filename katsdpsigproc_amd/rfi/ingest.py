@@ -10,12 +10,15 @@ samples left out, with a count and the OR of the flags per range and channel: al
 launch, bit for bit what :class:`.host.RangePercentilesHost` defines. And its companion: per
 baseline and for up to eight series of channel weights, the weighted means of the visibility and
 of its amplitude over the channels that carry data, with the weight sum, a count and the OR of
-the flags, every sample read once, bit for bit what :class:`.host.BandAverageHost` defines. The
-classes follow DESIGN.md, "Adding an operation".
+the flags, every sample read once, bit for bit what :class:`.host.BandAverageHost` defines. And
+the step in its middle, for a pipeline that holds several dumps: a block of up to eight dumps
+added to the accumulators of :class:`.device.Accumulate` in one launch that reads and writes
+them once, bit for bit what as many calls of :meth:`.host.AveragerHost.add` leave. The classes
+follow DESIGN.md, "Adding an operation".
 """
 
 import ctypes
-from typing import Any, Mapping, Optional, Tuple
+from typing import Any, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -650,3 +653,230 @@ class BandAverageHostFromDevice:
             ["series_flags"] if template.use_flags else [])  # fmt: skip
         out = _native_op.run_once(fn, self.command_queue, inputs, outputs)
         return out[0], out[1], out[2], out[3], (out[4] if template.use_flags else None)
+
+
+#: the most dumps one :class:`AccumulateBlock` launch adds
+MAX_DUMPS = 8
+
+
+class AccumulateBlockTemplate(_native_op.NativeTemplate):
+    """Add a block of up to `dumps` dumps to the accumulators of :class:`.device.Accumulate`
+    and :class:`.device.Finalise` in one kernel launch. For every sample the steps of
+    :meth:`host.AveragerHost.add` run on dump 0, then on dump 1 and so on, so the result is
+    bit for bit what as many launches of :class:`.device.Accumulate` leave, in that order;
+    but the accumulators, 26 of the 39 bytes a sample costs per dump, are read and written
+    once per block: 13 D + 26 bytes per sample for D dumps instead of 39 D.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    dumps
+        The most dumps a launch adds, 1 .. :data:`MAX_DUMPS` (``ValueError``): the operation
+        has that many sets of input slots
+    use_weights, input_flags
+        As for :class:`.device.AccumulateTemplate`
+    tuning
+        The kernel picks its launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.AveragerHost
+    KERNEL = "ksp_average_accumulate_block"
+
+    def __init__(self, context: AbstractContext, dumps: int, use_weights: bool = True,
+                 input_flags: host.BackgroundFlags = host.BackgroundFlags.NONE,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        if not 1 <= dumps <= MAX_DUMPS:
+            raise ValueError(f"dumps must be 1..{MAX_DUMPS}")
+        self.dumps = int(dumps)
+        self.use_weights = bool(use_weights)
+        self.input_flags = host.BackgroundFlags(input_flags)
+        self._setup(context, tuning)
+
+
+class AccumulateBlock(_native_op.NativeOperation):
+    """Concrete :class:`AccumulateBlockTemplate` (``ValueError`` if `channels` or `baselines`
+    is below 1). D stands for the template's `dumps`.
+
+    .. rubric:: Slots
+
+    **vis0** .. **vis{D-1}** : channels x baselines, complex64
+    **flags0** .. **flags{D-1}** : channels x baselines, uint8 (any non-zero byte means flagged)
+    **weights0** .. **weights{D-1}** : channels x baselines, float32 (only with ``use_weights``)
+    **input_flags0** .. **input_flags{D-1}** : channels x baselines, uint8 (only in FULL mode)
+    **input_flags** : channels, uint8 (only in CHANNEL mode: one mask for the block)
+    **acc_vis** : channels x baselines, complex64
+    **acc_weights** : channels x baselines, float32
+    **acc_flags** : channels x baselines, uint8
+
+    The kernel takes one row stride per kind, so the slots of one kind share one dimension
+    object for the baselines and get one padded size; each kind, and each accumulator, has a
+    dimension of its own. Every per-dump slot can so be compounded with the ``vis``,
+    ``input_flags`` or ``weights`` of a :class:`Prepare`, with the fused flagger's ``vis`` or
+    ``flags``, and the accumulators with :class:`.device.Finalise`'s.
+
+    :attr:`n_dumps`, the number of dumps the next call adds, starts at D and can be set to
+    1 .. D (``ValueError``) for the short block at the end of an integration. A call uses, and
+    allocates if need be, only the slots of the first `n_dumps` dumps.
+    """
+
+    def __init__(self, template: AccumulateBlockTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        if channels < 1 or baselines < 1:
+            raise ValueError("channels and baselines must be at least 1")
+        self._n_dumps = template.dumps
+
+        def per_dump(kind: str, dtype) -> None:
+            dim = accel.Dimension(baselines)
+            for d in range(template.dumps):
+                self.slots[f"{kind}{d}"] = accel.IOSlot((channels, dim), dtype)
+
+        per_dump("vis", np.complex64)
+        per_dump("flags", np.uint8)
+        if template.use_weights:
+            per_dump("weights", np.float32)
+        if template.input_flags == host.BackgroundFlags.FULL:
+            per_dump("input_flags", np.uint8)
+        elif template.input_flags == host.BackgroundFlags.CHANNEL:
+            self.slots["input_flags"] = accel.IOSlot((channels,), np.uint8)
+        for name, dtype in (("acc_vis", np.complex64), ("acc_weights", np.float32),
+                            ("acc_flags", np.uint8)):  # fmt: skip
+            self.slots[name] = accel.IOSlot((channels, accel.Dimension(baselines)), dtype)
+
+    @property
+    def n_dumps(self) -> int:
+        return self._n_dumps
+
+    @n_dumps.setter
+    def n_dumps(self, value: int) -> None:
+        if not 1 <= value <= self.template.dumps:
+            raise ValueError(f"n_dumps must be 1..{self.template.dumps}")
+        self._n_dumps = int(value)
+
+    def _used(self, name: str) -> bool:
+        """Whether a call with the present `n_dumps` touches slot `name`."""
+        digits = name.lstrip("abcdefghijklmnopqrstuvwxyz_")
+        return not digits or int(digits) < self._n_dumps
+
+    def ensure_all_bound(self) -> None:
+        for name, slot in self.slots.items():
+            if self._used(name) and not slot.is_bound():
+                slot.allocate(self.allocator)
+
+    def _dumps(self, kind: str) -> List[accel.DeviceArray]:
+        return [self.buffer(f"{kind}{d}") for d in range(self._n_dumps)]
+
+    @staticmethod
+    def _pointers(buffers: Sequence[accel.DeviceArray]):
+        """The host array of device pointers the launcher reads during the call."""
+        return (ctypes.c_void_p * len(buffers))(*[b.buffer.ptr for b in buffers])
+
+    def _run(self) -> None:
+        template = self.template
+        mode = template.input_flags
+        full = mode == host.BackgroundFlags.FULL
+        vis, flags = self._dumps("vis"), self._dumps("flags")
+        weights = self._dumps("weights") if template.use_weights else None
+        if full:
+            in_flags = self._dumps("input_flags")
+        elif mode:
+            in_flags = [self.buffer("input_flags")] * self._n_dumps
+        else:
+            in_flags = None
+        acc = [self.buffer(name) for name in ("acc_vis", "acc_weights", "acc_flags")]
+        self._launch(
+            np.int32(self._n_dumps),
+            self._pointers(vis),
+            self._pointers(flags),
+            self._pointers(weights) if weights is not None else None,
+            self._pointers(in_flags) if in_flags is not None else None,
+            np.int32(mode.value),
+            acc[0].buffer,
+            acc[1].buffer,
+            acc[2].buffer,
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(vis[0].padded_shape[1]),
+            np.int32(flags[0].padded_shape[1]),
+            np.int32(weights[0].padded_shape[1] if weights is not None else 0),
+            np.int32(in_flags[0].padded_shape[1] if full else 0),
+            np.int32(acc[0].padded_shape[1]),
+            np.int32(acc[1].padded_shape[1]),
+            np.int32(acc[2].padded_shape[1]),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        template = self.template
+        return self._parameters(dumps=template.dumps, use_weights=template.use_weights,
+                                input_flags=template.input_flags.name)  # fmt: skip
+
+
+AccumulateBlockTemplate.operation_class = AccumulateBlock
+
+
+class BlockAveragerHostFromDevice:
+    """Present an :class:`AccumulateBlockTemplate` and a :class:`.device.FinaliseTemplate`
+    like :class:`host.AveragerHost`, a block at a time: :meth:`add_block` takes sequences of
+    1 .. `dumps` arrays and does what as many calls of ``add`` do, :meth:`finalise` is the host
+    class's. The operations are instantiated and the shared accumulators allocated and zeroed
+    once, here; with a `finalise_template` built with ``clear=False`` the accumulators keep
+    their sums across :meth:`finalise`, unlike the host class."""
+
+    def __init__(self, block_template: AccumulateBlockTemplate, finalise_template,
+                 command_queue: AbstractCommandQueue, channels: int, baselines: int) -> None:  # fmt: skip
+        self.command_queue = command_queue
+        self.input_flags = block_template.input_flags
+        self.use_weights = block_template.use_weights
+        self.dumps = block_template.dumps
+        self._block = block_template.instantiate(command_queue, channels, baselines)
+        self._finalise = finalise_template.instantiate(command_queue, channels, baselines)
+        shared = ("acc_vis", "acc_weights", "acc_flags")
+        self._sequence = accel.OperationSequence(
+            command_queue, [("block", self._block), ("finalise", self._finalise)],
+            compounds={name: ["block:" + name, "finalise:" + name] for name in shared})
+        for name in shared:
+            self._sequence.ensure_bound(name)
+            self._sequence.buffer(name).zero(command_queue)
+
+    def add_block(self, vis: Sequence[np.ndarray], flags: Sequence[np.ndarray],
+                  weights: Optional[Sequence[Optional[np.ndarray]]] = None,
+                  input_flags: Optional[Sequence[np.ndarray]] = None) -> None:  # fmt: skip
+        """Add ``len(vis)`` dumps. `weights` is a sequence of that length (an entry of None:
+        weights of 1 for that dump) or None (1 for all); ``TypeError`` if it is given and the
+        template has no weights. `input_flags` is a sequence of that length exactly when the
+        template has a mask (``TypeError``); in CHANNEL mode the block has one mask, so its
+        entries must be equal (``ValueError``). ``ValueError`` unless there are 1 .. `dumps`
+        dumps and every sequence has as many entries."""
+        _native_op.check_optional(input_flags, self.input_flags, "input_flags")
+        if weights is not None and not self.use_weights:
+            raise TypeError("weights were provided but not included in the template")
+        n = len(vis)
+        if not 1 <= n <= self.dumps:
+            raise ValueError(f"a block has 1..{self.dumps} dumps, not {n}")
+        for what, given in (("flags", flags), ("weights", weights), ("input_flags", input_flags)):
+            if given is not None and len(given) != n:
+                raise ValueError(f"{what} has {len(given)} entries for {n} dumps")
+        fn = self._block
+        fn.n_dumps = n
+        inputs = {}
+        for d in range(n):
+            inputs[f"vis{d}"] = vis[d]
+            inputs[f"flags{d}"] = flags[d]
+            if self.use_weights:
+                w = weights[d] if weights is not None else None
+                inputs[f"weights{d}"] = w if w is not None else np.ones(np.shape(vis[d]), np.float32)
+            if self.input_flags == host.BackgroundFlags.FULL:
+                inputs[f"input_flags{d}"] = input_flags[d]
+        if self.input_flags == host.BackgroundFlags.CHANNEL:
+            if any(not np.array_equal(input_flags[0], mask) for mask in input_flags[1:]):
+                raise ValueError("in CHANNEL mode a block has one mask: the entries of "
+                                 "input_flags must be equal")
+            inputs["input_flags"] = input_flags[0]
+        _native_op.run_once(fn, self.command_queue, inputs, [])
+
+    def finalise(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        return tuple(_native_op.run_once(self._finalise, self.command_queue, {},
+                                         ["vis", "weights", "flags"]))  # fmt: skip
