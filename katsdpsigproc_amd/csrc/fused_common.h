@@ -1003,13 +1003,21 @@ __device__ __forceinline__ double mad_noise(const float (&dev)[R], int lane, dou
             const bool inexact = lane < n && e0 >= 0;
             stamp(11);
             if (debug_stop == 33) return x;
-            if (ksp_any(inexact)) {
+            // Rank on the float32 patterns first. Rounding to float32 is monotone, so sorting
+            // the candidates by pattern is also a (non-strict) sorting by exact value: the
+            // exact value of rank r belongs to a candidate whose pattern is k32, the pattern
+            // of rank r. When no inexact candidate has that pattern, every candidate that has
+            // it is exact and they all equal float(k32) -- which then IS the value of rank r,
+            // whatever the inexact candidates elsewhere in the bin round from. The same holds
+            // for p32 at rank r - 1, which only an even count with r >= 1 asks for. Only an
+            // inexact candidate AT one of the two patterns makes the exact values necessary
+            // (a window of loads per lane and a float64 ranking).
+            unsigned k32, p32;
+            rank_list_u32(lv, a32, n, r, lane, k32, p32, have_prev);
+            if (ksp_any(inexact && (a32 == k32 || (even && have_prev && a32 == p32)))) {
                 const double xe = fabs(exact_dev<WIDTH>(e0 & 0x7fffffff, fetch));
                 x = inexact ? xe : x;
             } else {
-                // every candidate's float32 value is the exact one: rank those
-                unsigned k32, p32;
-                rank_list_u32(lv, a32, n, r, lane, k32, p32, have_prev);
                 xk = (double)__uint_as_float(k32);
                 prev = (double)__uint_as_float(p32);
                 ranked = true;
@@ -1056,29 +1064,50 @@ __device__ __forceinline__ double mad_noise(const float (&dev)[R], int lane, dou
         __builtin_amdgcn_wave_barrier();
     }
     if (even && !have_prev) {
-        // r == 0: the lower median is the largest value below the bin, i.e. the
-        // largest exact value of the highest non-empty bin below K
-        int k2 = -1;
+        // r == 0: the lower median is the largest value below the bin. Its float32 value is
+        // the largest |dev| whose key is below K, i.e. whose pattern p is below
+        // T = ((K - 1) << 16) + 1 (the key is ceil(p / 65536), and K >= 1 here). All on the
+        // integer patterns: a NaN deviation, 0x7fc00000, stays above every T.
+        // Pass 1, two instructions per sample: w = 2 p - 2 T modulo 2^32 (the doubling
+        // drops the sign bit) lies in [2^32 - 2 T, 2^32 - 2] and grows with p for p < T,
+        // and in [0, 2^32 - 2 - 2 T] for T <= p <= 0x7fffffff, so the unsigned maximum of
+        // w, started at 2^32 - 2 T (p = 0), is 2 b - 2 T for b = max(p < T ? p : 0).
+        // (Each dev[j] goes through an asm of its own, as dv() would have it: no key or
+        // pattern of the search above is kept alive for this.)
+        const unsigned bias = 0u - 2u * (((K - 1) << 16) + 1u);
+        unsigned wmax0 = bias, wmax1 = bias;
 #pragma unroll
         for (int j = 0; j < R; j++) {
-            const int kj = (int)key_of(j);
-            k2 = (kj < (int)K) ? max(k2, kj) : k2;
+            unsigned w;
+            asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(w) : "v"(dev[j]), "s"(bias));
+            if (j & 1)
+                wmax1 = max(wmax1, w);
+            else
+                wmax0 = max(wmax0, w);
         }
-        k2 = wave_max_int(k2);
-        // (nothing with a non-zero key below the bin: the value below it is a +-2^-150 --
-        // were there none, an even count could not have its lower median down here)
-        const bool below_is_tiny = k2 <= 0;
-        unsigned long long bm = bin_mask((unsigned)(below_is_tiny ? 0 : k2));
-        // within that bin the largest float32 values are enough
-        float b32 = 0.0f;
-#pragma unroll
-        for (int j = 0; j < R; j++)
-            if ((bm >> j) & 1) b32 = fmaxf(b32, fabsf(dv(j)));
-        b32 = ksp_wave_max(b32);
+        const unsigned b2 = ksp_wave_max(max(wmax0, wmax1)) - bias;  // 2 b
+        const float b32 = __uint_as_float(b2 >> 1);
+        // (only samples with key 0 have pattern 0. Nothing with a non-zero key below the bin:
+        // the value below it is a +-2^-150 -- were there none, an even count could not have
+        // its lower median down here)
+        const bool below_is_tiny = b2 == 0;
+        // Pass 2, three per sample: which samples are at that value, 2 p == 2 b.
+        // mask = 2 * mask + (compare): v_cmp into vcc, v_addc folds it in
         unsigned long long top = 0;
+        if (!below_is_tiny) {
+            unsigned t_lo = 0, t_hi = 0, p2;
 #pragma unroll
-        for (int j = 0; j < R; j++)
-            if (((bm >> j) & 1) && fabsf(dv(j)) == b32) top |= 1ull << j;
+            for (int j = (R < 32 ? R : 32) - 1; j >= 0; j--)
+                asm("v_lshlrev_b32 %1, 1, %2\n\tv_cmp_eq_u32 vcc, %3, %1\n\t"
+                    "v_addc_co_u32 %0, vcc, %0, %0, vcc"
+                    : "+v"(t_lo), "=&v"(p2) : "v"(dev[j]), "s"(b2) : "vcc");
+#pragma unroll
+            for (int j = R - 1; j >= 32; j--)
+                asm("v_lshlrev_b32 %1, 1, %2\n\tv_cmp_eq_u32 vcc, %3, %1\n\t"
+                    "v_addc_co_u32 %0, vcc, %0, %0, vcc"
+                    : "+v"(t_hi), "=&v"(p2) : "v"(dev[j < R ? j : 0]), "s"(b2) : "vcc");
+            top = ((unsigned long long)t_hi << 32) | t_lo;
+        }
         bool recompute = true;
         if (below_is_tiny) {
             prev = 0x1p-150;
