@@ -542,6 +542,39 @@ int ksp_compress_weights(int device, void *stream, const float *weights, uint8_t
                          float *weights_channel, int channels, int baselines,
                          int weights_stride, int weights8_stride);
 
+/* apply_gains: per-input gain corrections applied to visibilities, weights and flags, in one
+ * launch (no reference counterpart; bit for bit what rfi/host.py ApplyGainsHost computes;
+ * every float step is one float32 operation, rounded once, a multiply then an add, never an
+ * fma).
+ * vis, out_vis: complex64 [channels][stride]; weights, out_weights: float32; flags, out_flags:
+ * uint8; gains: complex64 [channels][gains_stride], of which n_inputs per row are data: the
+ * correction that multiplies; inputs: int32 [baselines][2], contiguous: the two inputs of every
+ * baseline. Baselines contiguous, one stride per array, in elements. Per channel c and
+ * baseline j, with a = inputs[j][0], b = inputs[j][1]:
+ *   inr = 0 <= a < n_inputs and 0 <= b < n_inputs;  ga = gains[c][a], gb = gains[c][b];
+ *   cr = ga.re gb.re + ga.im gb.im;  ci = ga.im gb.re - ga.re gb.im;        (ga conj(gb))
+ *   ok = inr and neither cr nor ci is NaN;  p = cr cr + ci ci;
+ *   out_vis[c][j] = ok ? (v.re cr - v.im ci, v.re ci + v.im cr) : v, v = vis[c][j];
+ *   out_weights[c][j] = ok and p > 0 ? weights[c][j] / p : 0 (correctly rounded);
+ *   out_flags[c][j] = flags[c][j] | (ok ? 0 : flag_value).
+ * Any int32 is allowed in inputs: an index outside 0 .. n_inputs - 1 is never used to form an
+ * address, and its samples are treated like those of a NaN gain: vis passes through bit for
+ * bit, the weight becomes 0 and flag_value is set. weights and out_weights are both NULL or
+ * both given, and so are flags and out_flags. An output may be its input (the same pointer
+ * with the same stride: in place); otherwise it must share no byte with it. gains and inputs
+ * must not overlap any output. n_inputs is 1..4096, flag_value 1..255, channels and baselines
+ * at least 1. Elements between baselines (or n_inputs) and a stride are neither read nor
+ * written. 16-byte accesses need every sample array given, and every row start of it, to be a
+ * multiple of 16 bytes (and inputs to be one, for its own loads); anything else takes a slower
+ * element-wise path with the same result. One kernel launch, no workspace. Every argument is
+ * checked before any device call. */
+int ksp_apply_gains(int device, void *stream, const void *vis, const float *weights,
+                    const uint8_t *flags, const void *gains, const int32_t *inputs,
+                    void *out_vis, float *out_weights, uint8_t *out_flags, int channels,
+                    int baselines, int n_inputs, int vis_stride, int weights_stride,
+                    int flags_stride, int gains_stride, int out_vis_stride,
+                    int out_weights_stride, int out_flags_stride, int flag_value);
+
 /* range_percentiles: per channel and per range of baselines, the [0, 100, 25, 75, 50] %
  * amplitudes ("lower" element) of the samples that are neither NaN nor flagged under a mask,
  * how many those are, and the OR of the range's flags, all ranges in one launch (no reference

@@ -15,8 +15,8 @@
 // with and dropped. `wide` is an ordinary bool: where it is a constant at the call site, the
 // other path folds away.
 //
-// compress_weights.hip, flag_count.hip and the row pass of sir.hip are written on these
-// helpers. average.hip and prepare.hip have the same layout but hold several arrays of a run
+// compress_weights.hip, flag_count.hip, apply_gains.hip and the row pass of sir.hip are written
+// on these helpers. average.hip and prepare.hip have the same layout but hold several arrays of a run
 // at once, and keep their own two paths (profiles/run16.md).
 #pragma once
 
@@ -41,6 +41,24 @@ __device__ __forceinline__ void ksp_run_load(const T *p, int valid, bool wide, T
     } else {
 #pragma unroll
         for (int i = 0; i < KSP_RUN; i++) v[i] = i < valid ? T(p[i]) : fill;
+    }
+}
+
+// The other way: the first `valid` elements of a run are stored, the rest dropped.
+template <typename T>
+__device__ __forceinline__ void ksp_run_store(T *p, int valid, bool wide, const T (&v)[KSP_RUN])
+{
+    if (wide && valid >= KSP_RUN) {
+#pragma unroll
+        for (int q = 0; q < (int)sizeof(v) / 16; q++) {
+            ksp_run_bytes t;
+            __builtin_memcpy(&t, &v[q * (16 / sizeof(T))], 16);
+            reinterpret_cast<ksp_run_bytes *>(p)[q] = t;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < KSP_RUN; i++)
+            if (i < valid) p[i] = v[i];
     }
 }
 

@@ -631,6 +631,97 @@ class CompressWeightsHost:
             return weights8.astype(np.float32) * weights_channel[:, np.newaxis]
 
 
+class ApplyGainsHost:
+    """Per-input gain corrections applied to averaged visibilities, with the weights scaled to
+    match and the samples without a correction flagged: what every consumer of calibrated data
+    wants between :class:`AveragerHost` and the 2-D flagger or :class:`CompressWeightsHost`. No
+    reference counterpart; this class is the definition that the device operation
+    (:class:`.ingest.ApplyGainsTemplate`) matches bit for bit.
+
+    ``gains[c, i]`` is the correction that *multiplies*: a caller with solved gains inverts them
+    and combines bandpass, delay and gain on that small array first. ``inputs[j]`` names the two
+    inputs ``(a, b)`` of baseline ``j``. Per channel ``c`` and baseline ``j``, every float step
+    one float32 operation, rounded once (a multiply, then an add, never an fma; real and
+    imaginary parts apart, not a complex multiply)::
+
+        inr = 0 <= a < n_inputs and 0 <= b < n_inputs
+        ga, gb = gains[c, a], gains[c, b]                 (not looked up unless inr)
+        cr = ga.re*gb.re + ga.im*gb.im;  ci = ga.im*gb.re - ga.re*gb.im        (ga * conj(gb))
+        ok = inr and cr is not NaN and ci is not NaN
+        p  = cr*cr + ci*ci
+        out_vis     = ok ? (v.re*cr - v.im*ci, v.re*ci + v.im*cr) : v
+        out_weights = ok and p > 0 ? w / p : 0
+        out_flags   = flags | (ok ? 0 : flag_value)
+
+    What follows from it:
+
+    * Without a correction (a NaN in it, or an index outside the gains; any int32 is allowed in
+      `inputs`) the visibility passes through bit for bit, the weight becomes 0 and the sample
+      is flagged.
+    * Infinities and denormals go through as IEEE gives them: an infinite ``p`` makes a finite
+      weight 0, and a correction whose parts subtract to ``inf - inf`` is a NaN correction.
+    * An autocorrelation (``a == b``) with a finite gain has ``ci == +0`` exactly.
+    * A zero correction (or one whose ``p`` underflows to 0) gives weight 0, "no data" as
+      :class:`AveragerHost` reads it, and no flag.
+
+    Parameters
+    ----------
+    flag_value
+        Bits set in ``out_flags`` of a sample without a correction, 1..255
+        (:func:`check_flag_byte`)
+    """
+
+    MAX_INPUTS = 4096
+
+    def __init__(self, flag_value: int = 128) -> None:
+        self.flag_value = check_flag_byte("flag_value", flag_value)
+
+    def __call__(self, vis: np.ndarray, gains: np.ndarray, inputs: np.ndarray,
+                 weights: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None):  # fmt: skip
+        """``(out_vis, out_weights or None, out_flags or None)`` for complex64 `vis` (channels,
+        baselines), complex64 `gains` (channels, n_inputs), int32 `inputs` (baselines, 2),
+        optional float32 `weights` and optional uint8 `flags` (both channels, baselines).
+        ``ValueError``, naming the argument, for a wrong dtype, rank or shape (channels and
+        baselines at least 1, n_inputs 1..4096). No argument is modified."""
+        vis = _check_array("vis", vis, np.complex64, "(channels, baselines)",
+                           lambda s: len(s) == 2 and s[0] >= 1 and s[1] >= 1)  # fmt: skip
+        channels, baselines = vis.shape
+        gains = _check_array("gains", gains, np.complex64, "(channels, n_inputs), n_inputs 1..4096",
+                             lambda s: len(s) == 2 and s[0] == channels
+                             and 1 <= s[1] <= self.MAX_INPUTS)  # fmt: skip
+        inputs = _check_array("inputs", inputs, np.int32, "(baselines, 2)",
+                              lambda s: s == (baselines, 2))  # fmt: skip
+        if weights is not None:
+            weights = _check_array("weights", weights, np.float32, "(channels, baselines)",
+                                   lambda s: s == vis.shape)  # fmt: skip
+        if flags is not None:
+            flags = _check_array("flags", flags, np.uint8, "(channels, baselines)",
+                                 lambda s: s == vis.shape)  # fmt: skip
+        n_inputs = gains.shape[1]
+        inr = ((inputs >= 0) & (inputs < n_inputs)).all(axis=1)
+        ga = gains[:, np.where(inr, inputs[:, 0], 0)]
+        gb = gains[:, np.where(inr, inputs[:, 1], 0)]
+        with np.errstate(all="ignore"):
+            cr = ga.real * gb.real + ga.imag * gb.imag
+            ci = ga.imag * gb.real - ga.real * gb.imag
+            ok = inr[np.newaxis, :] & ~np.isnan(cr) & ~np.isnan(ci)
+            p = cr * cr + ci * ci
+            out_vis = np.empty((channels, baselines), np.complex64)
+            out_vis.real[...] = np.where(ok, vis.real * cr - vis.imag * ci, vis.real)
+            out_vis.imag[...] = np.where(ok, vis.real * ci + vis.imag * cr, vis.imag)
+            assert cr.dtype == np.float32 and p.dtype == np.float32
+            out_weights = None
+            if weights is not None:
+                scaled = ok & (p > 0)
+                # (the divisor of a sample that gets no weight is 1, not p: no 0 / 0)
+                out_weights = np.where(scaled, weights / np.where(scaled, p, np.float32(1)),
+                                       np.float32(0))  # fmt: skip
+        out_flags = None
+        if flags is not None:
+            out_flags = flags | np.where(ok, np.uint8(0), np.uint8(self.flag_value))
+        return out_vis, out_weights, out_flags
+
+
 def check_ranges(ranges, baselines: Optional[int] = None) -> Tuple[Tuple[int, int], ...]:
     """`ranges` as a tuple of 1 to :attr:`RangePercentilesHost.MAX_RANGES` pairs of ints
     ``(start, stop)`` with ``0 <= start <= stop``, ``stop - start`` at most

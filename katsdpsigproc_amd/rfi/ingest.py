@@ -13,8 +13,10 @@ of its amplitude over the channels that carry data, with the weight sum, a count
 the flags, every sample read once, bit for bit what :class:`.host.BandAverageHost` defines. And
 the step in its middle, for a pipeline that holds several dumps: a block of up to eight dumps
 added to the accumulators of :class:`.device.Accumulate` in one launch that reads and writes
-them once, bit for bit what as many calls of :meth:`.host.AveragerHost.add` leave. The classes
-follow DESIGN.md, "Adding an operation".
+them once, bit for bit what as many calls of :meth:`.host.AveragerHost.add` leave. And the step
+between averaging and the consumers of calibrated data: per-input gain corrections applied to
+``vis``, ``weights`` and ``flags`` in one launch, in place or not, bit for bit what
+:class:`.host.ApplyGainsHost` defines. The classes follow DESIGN.md, "Adding an operation".
 """
 
 import ctypes
@@ -352,6 +354,147 @@ class CompressWeightsHostFromDevice:
         out = _native_op.run_once(fn, self.command_queue, {"weights": weights},
                                   ["weights8", "weights_channel"])  # fmt: skip
         return out[0], out[1]
+
+
+class ApplyGainsTemplate(_native_op.NativeTemplate):
+    """The step between averaging and what consumes calibrated data: the per-input gain
+    corrections applied to the ``vis`` that :class:`.device.Finalise` leaves, the ``weights``
+    scaled to match and the samples without a correction flagged, in one kernel launch; see
+    :class:`host.ApplyGainsHost` for every step. The gains are small (channels x inputs) and
+    stay on the device; only their application is per sample.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    weights
+        ``True``: there are a `weights` and an `out_weights` slot
+    flags
+        ``True``: there are a `flags` and an `out_flags` slot
+    flag_value
+        As for :class:`host.ApplyGainsHost` (same errors)
+    tuning
+        The kernel picks its launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.ApplyGainsHost
+    KERNEL = "ksp_apply_gains"
+
+    def __init__(self, context: AbstractContext, weights: bool = True, flags: bool = True,
+                 flag_value: int = 128, tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        self.weights = bool(weights)
+        self.flags = bool(flags)
+        self.flag_value = host.ApplyGainsHost(flag_value).flag_value
+        self._setup(context, tuning)
+
+
+class ApplyGains(_native_op.NativeOperation):
+    """Concrete :class:`ApplyGainsTemplate` (``ValueError`` if `channels` or `baselines` is
+    below 1 or `n_inputs` outside 1..4096).
+
+    .. rubric:: Slots
+
+    **vis**, **out_vis** : channels x baselines, complex64
+    **weights**, **out_weights** : channels x baselines, float32 (only with ``weights``)
+    **flags**, **out_flags** : channels x baselines, uint8 (only with ``flags``)
+    **gains** : channels x n_inputs, complex64: the corrections that multiply
+    **inputs** : baselines x 2, int32, contiguous: the two inputs of every baseline
+
+    Every padded dimension is an object of its own, so ``vis``, ``weights`` and ``flags`` can
+    be compounded with :class:`.device.Finalise`'s (or :class:`Prepare`'s) outputs and the
+    ``out_*`` slots with the inputs of :class:`CompressWeights`, :class:`RangePercentiles` or
+    the 2-D flagger, each taking the other's padding. Binding one buffer to ``vis`` and
+    ``out_vis`` (and likewise to the other two pairs) applies the gains in place; with buffers
+    of their own the inputs are left untouched.
+    """
+
+    def __init__(self, template: ApplyGainsTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int, n_inputs: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        if channels < 1 or baselines < 1:
+            raise ValueError("channels and baselines must be at least 1")
+        if not 1 <= n_inputs <= host.ApplyGainsHost.MAX_INPUTS:
+            raise ValueError(f"n_inputs must be 1..{host.ApplyGainsHost.MAX_INPUTS}")
+        self.n_inputs = n_inputs
+
+        def pair(name: str, dtype) -> None:
+            for slot in (name, "out_" + name):
+                self.slots[slot] = accel.IOSlot((channels, accel.Dimension(baselines)), dtype)
+
+        pair("vis", np.complex64)
+        if template.weights:
+            pair("weights", np.float32)
+        if template.flags:
+            pair("flags", np.uint8)
+        self.slots["gains"] = accel.IOSlot((channels, accel.Dimension(n_inputs)), np.complex64)
+        self.slots["inputs"] = accel.IOSlot(
+            (accel.Dimension(baselines), accel.Dimension(2, exact=True)), np.int32)  # fmt: skip
+
+    def _run(self) -> None:
+        template = self.template
+        vis, out_vis = self.buffer("vis"), self.buffer("out_vis")
+        weights = self.buffer("weights") if template.weights else None
+        out_weights = self.buffer("out_weights") if template.weights else None
+        flags = self.buffer("flags") if template.flags else None
+        out_flags = self.buffer("out_flags") if template.flags else None
+        gains = self.buffer("gains")
+        self._launch(
+            vis.buffer,
+            weights.buffer if weights is not None else None,
+            flags.buffer if flags is not None else None,
+            gains.buffer,
+            self.buffer("inputs").buffer,
+            out_vis.buffer,
+            out_weights.buffer if out_weights is not None else None,
+            out_flags.buffer if out_flags is not None else None,
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(self.n_inputs),
+            np.int32(vis.padded_shape[1]),
+            np.int32(weights.padded_shape[1] if weights is not None else 0),
+            np.int32(flags.padded_shape[1] if flags is not None else 0),
+            np.int32(gains.padded_shape[1]),
+            np.int32(out_vis.padded_shape[1]),
+            np.int32(out_weights.padded_shape[1] if out_weights is not None else 0),
+            np.int32(out_flags.padded_shape[1] if out_flags is not None else 0),
+            np.int32(template.flag_value),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        template = self.template
+        return self._parameters(weights=template.weights, flags=template.flags,
+                                flag_value=template.flag_value, n_inputs=self.n_inputs)  # fmt: skip
+
+
+ApplyGainsTemplate.operation_class = ApplyGains
+
+
+class ApplyGainsHostFromDevice:
+    """Make an :class:`ApplyGainsTemplate` callable like :class:`host.ApplyGainsHost`:
+    ``(vis, gains, inputs, weights=None, flags=None)`` in, ``(out_vis, out_weights or None,
+    out_flags or None)`` out; allocates on every call. ``TypeError`` unless `weights` and
+    `flags` are each given exactly when the template has them."""
+
+    def __init__(self, template: ApplyGainsTemplate, command_queue: AbstractCommandQueue) -> None:
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, vis: np.ndarray, gains: np.ndarray, inputs: np.ndarray,
+                 weights: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None
+                 ) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:  # fmt: skip
+        template = self.template
+        _native_op.check_optional(weights, template.weights, "weights")
+        _native_op.check_optional(flags, template.flags, "flags")
+        channels, baselines = vis.shape
+        fn = template.instantiate(self.command_queue, channels, baselines, np.shape(gains)[-1])
+        given = {"vis": vis, "gains": gains, "inputs": inputs, "weights": weights, "flags": flags}
+        outputs = ["out_vis"] + (["out_weights"] if template.weights else []) + (
+            ["out_flags"] if template.flags else [])  # fmt: skip
+        out = _native_op.run_once(fn, self.command_queue, given, outputs)
+        return (out[0], out[1] if template.weights else None,
+                out[-1] if template.flags else None)  # fmt: skip
 
 
 class RangePercentilesTemplate(_native_op.NativeTemplate):
