@@ -6,6 +6,8 @@ written down once. Private: the public classes live in the modules that use thes
 
 from typing import Any, List, Mapping, Optional, Sequence, Tuple
 
+import numpy as np
+
 from . import accel, tune
 from .abc import AbstractCommandQueue, AbstractContext
 
@@ -71,6 +73,17 @@ class NativeOperation(accel.Operation):
     def _parameters(self, **own) -> Mapping[str, Any]:
         """`own` and the shape: what :meth:`parameters` returns."""
         return {**own, "channels": self.channels, "baselines": self.baselines}
+
+
+def pointer(array: Optional[accel.DeviceArray]):
+    """The launch argument for the data of `array`: None for an optional slot that is absent."""
+    return array.buffer if array is not None else None
+
+
+def stride(array: Optional[accel.DeviceArray], axis: int = 1) -> np.int32:
+    """The launch argument for the padded length of `array` along `axis`, the row stride of
+    a two-dimensional slot: 0 for an optional slot that is absent."""
+    return np.int32(array.padded_shape[axis] if array is not None else 0)
 
 
 def run_once(fn: accel.Operation, queue: AbstractCommandQueue, inputs: Mapping[str, Any],

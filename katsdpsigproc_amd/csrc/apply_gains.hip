@@ -208,10 +208,13 @@ extern "C" int ksp_apply_gains(int device, void *stream, const void *vis, const 
                                int out_vis_stride, int out_weights_stride, int out_flags_stride,
                                int flag_value)
 {
-    KSP_REQUIRE(vis != nullptr, "vis is NULL");
-    KSP_REQUIRE(gains != nullptr, "gains is NULL");
-    KSP_REQUIRE(inputs != nullptr, "inputs is NULL");
-    KSP_REQUIRE(out_vis != nullptr, "out_vis is NULL");
+    const ksp_plane in = {"vis", vis, vis_stride, 8}, out = {"out_vis", out_vis, out_vis_stride, 8};
+    const ksp_plane table = {"gains", gains, gains_stride, 8};
+    const ksp_planes pairs = {{"weights", weights, weights_stride, 4, true},
+                              {"out_weights", out_weights, out_weights_stride, 4, true},
+                              {"flags", flags, flags_stride, 1, true},
+                              {"out_flags", out_flags, out_flags_stride, 1, true}};
+    KSP_TRY(ksp_planes_given({in, table, {"inputs", inputs, 0, 4}, out}));
     KSP_REQUIRE((weights == nullptr) == (out_weights == nullptr),
                 "weights and out_weights must both be NULL or both be given");
     KSP_REQUIRE((flags == nullptr) == (out_flags == nullptr),
@@ -220,17 +223,9 @@ extern "C" int ksp_apply_gains(int device, void *stream, const void *vis, const 
     KSP_REQUIRE(baselines >= 1, "baselines must be at least 1");
     KSP_REQUIRE(n_inputs >= 1 && n_inputs <= AG_MAX_INPUTS, "n_inputs must be 1..4096");
     KSP_REQUIRE(flag_value >= 1 && flag_value <= 255, "flag_value must be 1..255");
-    KSP_REQUIRE(vis_stride >= baselines, "vis_stride is smaller than baselines");
-    KSP_REQUIRE(out_vis_stride >= baselines, "out_vis_stride is smaller than baselines");
-    KSP_REQUIRE(gains_stride >= n_inputs, "gains_stride is smaller than n_inputs");
-    KSP_REQUIRE(weights == nullptr || weights_stride >= baselines,
-                "weights_stride is smaller than baselines");
-    KSP_REQUIRE(weights == nullptr || out_weights_stride >= baselines,
-                "out_weights_stride is smaller than baselines");
-    KSP_REQUIRE(flags == nullptr || flags_stride >= baselines,
-                "flags_stride is smaller than baselines");
-    KSP_REQUIRE(flags == nullptr || out_flags_stride >= baselines,
-                "out_flags_stride is smaller than baselines");
+    KSP_TRY(ksp_planes_hold({in, out}, baselines, "baselines"));
+    KSP_TRY(ksp_planes_hold({table}, n_inputs, "n_inputs"));
+    KSP_TRY(ksp_planes_hold(pairs, baselines, "baselines"));
     KSP_REQUIRE(ag_same_or_apart(vis, vis_stride, out_vis, out_vis_stride, channels, baselines, 8),
                 "out_vis overlaps vis without being vis with the same stride");
     KSP_REQUIRE(weights == nullptr ||
@@ -242,14 +237,9 @@ extern "C" int ksp_apply_gains(int device, void *stream, const void *vis, const 
                 "out_flags overlaps flags without being flags with the same stride");
     const ag_geometry geom = ag_make_geometry(channels, baselines);
     KSP_REQUIRE(geom.groups <= 0x7fffffffll, "array too large for one launch");
+    // (the rows of gains are read element by element; inputs has a flag of its own)
     const int aligned =
-        (ksp_rows_aligned(vis, vis_stride, 8) && ksp_rows_aligned(out_vis, out_vis_stride, 8) &&
-                 ksp_rows_aligned_if_given(weights, weights_stride, 4) &&
-                 ksp_rows_aligned_if_given(out_weights, out_weights_stride, 4) &&
-                 ksp_rows_aligned_if_given(flags, flags_stride, 1) &&
-                 ksp_rows_aligned_if_given(out_flags, out_flags_stride, 1)
-             ? AG_ALIGNED_DATA
-             : 0) |
+        (ksp_planes_aligned({in, out}) && ksp_planes_aligned(pairs) ? AG_ALIGNED_DATA : 0) |
         ((uintptr_t)inputs % 16 == 0 ? AG_ALIGNED_INPUTS : 0);
 
     KSP_CHECK(hipSetDevice(device));

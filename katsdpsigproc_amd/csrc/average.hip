@@ -260,26 +260,6 @@ __global__ __launch_bounds__(AVG_THREADS) void average_finalise_kernel(
     }
 }
 
-template <bool HAS_W>
-static void avg_launch_accumulate(int mode, dim3 grid, hipStream_t stream, const float2 *vis,
-                                  const uint8_t *flags, const float *weights,
-                                  const uint8_t *input_flags, float2 *acc_vis, float *acc_weights,
-                                  uint8_t *acc_flags, long long runs, int runs_per_row,
-                                  int baselines, int vis_stride, int flags_stride,
-                                  int weights_stride, int input_flags_stride, int acc_vis_stride,
-                                  int acc_weights_stride, int acc_flags_stride, int aligned)
-{
-    // (mode is 0 .. 2 here)
-    ksp_dispatch_exact<0, 1, 2>(mode, [&](auto MODE) {
-        hipLaunchKernelGGL((average_accumulate_kernel<HAS_W, MODE()>), grid, dim3(AVG_THREADS), 0,
-                           stream, vis, flags, weights, input_flags, acc_vis, acc_weights,
-                           acc_flags, runs, runs_per_row, baselines, (long long)vis_stride,
-                           (long long)flags_stride, (long long)weights_stride,
-                           (long long)input_flags_stride, (long long)acc_vis_stride,
-                           (long long)acc_weights_stride, (long long)acc_flags_stride, aligned);
-    });
-}
-
 extern "C" int ksp_average_accumulate(int device, void *stream, const void *vis,
                                       const uint8_t *flags, const float *weights,
                                       const uint8_t *input_flags, int input_flags_mode,
@@ -289,11 +269,16 @@ extern "C" int ksp_average_accumulate(int device, void *stream, const void *vis,
                                       int input_flags_stride, int acc_vis_stride,
                                       int acc_weights_stride, int acc_flags_stride)
 {
-    KSP_REQUIRE(vis != nullptr, "vis is NULL");
-    KSP_REQUIRE(flags != nullptr, "flags is NULL");
-    KSP_REQUIRE(acc_vis != nullptr, "acc_vis is NULL");
-    KSP_REQUIRE(acc_weights != nullptr, "acc_weights is NULL");
-    KSP_REQUIRE(acc_flags != nullptr, "acc_flags is NULL");
+    // (input_flags has a row stride only as one byte per sample, and checks of its own)
+    const ksp_planes planes = {
+        {"vis", vis, vis_stride, 8},
+        {"flags", flags, flags_stride, 1},
+        {"weights", weights, weights_stride, 4, true},
+        {"input_flags", input_flags_mode == 2 ? input_flags : nullptr, input_flags_stride, 1, true},
+        {"acc_vis", acc_vis, acc_vis_stride, 8},
+        {"acc_weights", acc_weights, acc_weights_stride, 4},
+        {"acc_flags", acc_flags, acc_flags_stride, 1}};
+    KSP_TRY(ksp_planes_given(planes));
     KSP_REQUIRE(input_flags_mode >= 0 && input_flags_mode <= 2,
                 "input_flags_mode must be 0 (none), 1 (per channel) or 2 (per sample)");
     KSP_REQUIRE(input_flags_mode == 0 || input_flags != nullptr,
@@ -302,43 +287,25 @@ extern "C" int ksp_average_accumulate(int device, void *stream, const void *vis,
                 "input_flags given but input_flags_mode is 0");
     KSP_REQUIRE(channels >= 1, "channels must be at least 1");
     KSP_REQUIRE(baselines >= 1, "baselines must be at least 1");
-    KSP_REQUIRE(vis_stride >= baselines, "vis_stride is smaller than baselines");
-    KSP_REQUIRE(flags_stride >= baselines, "flags_stride is smaller than baselines");
-    KSP_REQUIRE(weights == nullptr || weights_stride >= baselines,
-                "weights_stride is smaller than baselines");
-    KSP_REQUIRE(input_flags_mode != 2 || input_flags_stride >= baselines,
-                "input_flags_stride is smaller than baselines");
-    KSP_REQUIRE(acc_vis_stride >= baselines, "acc_vis_stride is smaller than baselines");
-    KSP_REQUIRE(acc_weights_stride >= baselines, "acc_weights_stride is smaller than baselines");
-    KSP_REQUIRE(acc_flags_stride >= baselines, "acc_flags_stride is smaller than baselines");
-    const int runs_per_row = ksp_divup(baselines, AVG_RUN);
-    const long long runs = (long long)channels * runs_per_row;
-    const long long groups = (runs + AVG_THREADS - 1) / AVG_THREADS;
-    KSP_REQUIRE(groups <= 0x7fffffffll, "array too large for one launch");
-    const int aligned =
-        ksp_rows_aligned_if_given(vis, vis_stride, 8) &&
-        ksp_rows_aligned_if_given(flags, flags_stride, 1) &&
-        ksp_rows_aligned_if_given(weights, weights_stride, 4) &&
-        (input_flags_mode != 2 || ksp_rows_aligned_if_given(input_flags, input_flags_stride, 1)) &&
-        ksp_rows_aligned_if_given(acc_vis, acc_vis_stride, 8) &&
-        ksp_rows_aligned_if_given(acc_weights, acc_weights_stride, 4) &&
-        ksp_rows_aligned_if_given(acc_flags, acc_flags_stride, 1);
+    KSP_TRY(ksp_planes_hold(planes, baselines, "baselines"));
+    ksp_run_grid g;
+    KSP_TRY(ksp_make_run_grid(channels, baselines, AVG_RUN, AVG_THREADS, g));
+    const int aligned = ksp_planes_aligned(planes);
 
     KSP_CHECK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)groups);
-    if (weights != nullptr)
-        avg_launch_accumulate<true>(input_flags_mode, grid, s, (const float2 *)vis, flags, weights,
-                                    input_flags, (float2 *)acc_vis, acc_weights, acc_flags, runs,
-                                    runs_per_row, baselines, vis_stride, flags_stride,
-                                    weights_stride, input_flags_stride, acc_vis_stride,
-                                    acc_weights_stride, acc_flags_stride, aligned);
-    else
-        avg_launch_accumulate<false>(input_flags_mode, grid, s, (const float2 *)vis, flags, weights,
-                                     input_flags, (float2 *)acc_vis, acc_weights, acc_flags, runs,
-                                     runs_per_row, baselines, vis_stride, flags_stride,
-                                     weights_stride, input_flags_stride, acc_vis_stride,
-                                     acc_weights_stride, acc_flags_stride, aligned);
+    ksp_dispatch_bool(weights != nullptr, [&](auto HAS_W) {
+        // (input_flags_mode is 0 .. 2 here)
+        ksp_dispatch_exact<0, 1, 2>(input_flags_mode, [&](auto MODE) {
+            hipLaunchKernelGGL(
+                (average_accumulate_kernel<decltype(HAS_W)::value, MODE()>),
+                dim3((unsigned)g.groups), dim3(AVG_THREADS), 0, (hipStream_t)stream,
+                (const float2 *)vis, flags, weights, input_flags, (float2 *)acc_vis, acc_weights,
+                acc_flags, g.runs, g.runs_per_row, baselines, (long long)vis_stride,
+                (long long)flags_stride, (long long)weights_stride,
+                (long long)input_flags_stride, (long long)acc_vis_stride,
+                (long long)acc_weights_stride, (long long)acc_flags_stride, aligned);
+        });
+    });
     KSP_LAUNCH_CHECK();
     return 0;
 }
@@ -351,51 +318,33 @@ extern "C" int ksp_average_finalise(int device, void *stream, void *acc_vis, flo
                                     int out_vis_stride, int out_weights_stride,
                                     int out_flags_stride)
 {
-    KSP_REQUIRE(acc_vis != nullptr, "acc_vis is NULL");
-    KSP_REQUIRE(acc_weights != nullptr, "acc_weights is NULL");
-    KSP_REQUIRE(acc_flags != nullptr, "acc_flags is NULL");
-    KSP_REQUIRE(out_vis != nullptr, "out_vis is NULL");
-    KSP_REQUIRE(out_weights != nullptr, "out_weights is NULL");
-    KSP_REQUIRE(out_flags != nullptr, "out_flags is NULL");
+    const ksp_planes planes = {{"acc_vis", acc_vis, acc_vis_stride, 8},
+                               {"acc_weights", acc_weights, acc_weights_stride, 4},
+                               {"acc_flags", acc_flags, acc_flags_stride, 1},
+                               {"out_vis", out_vis, out_vis_stride, 8},
+                               {"out_weights", out_weights, out_weights_stride, 4},
+                               {"out_flags", out_flags, out_flags_stride, 1}};
+    KSP_TRY(ksp_planes_given(planes));
     KSP_REQUIRE(channels >= 1, "channels must be at least 1");
     KSP_REQUIRE(baselines >= 1, "baselines must be at least 1");
     KSP_REQUIRE(channel_factor >= 1, "channel_factor must be at least 1");
     KSP_REQUIRE(channels % channel_factor == 0, "channel_factor does not divide channels");
-    KSP_REQUIRE(acc_vis_stride >= baselines, "acc_vis_stride is smaller than baselines");
-    KSP_REQUIRE(acc_weights_stride >= baselines, "acc_weights_stride is smaller than baselines");
-    KSP_REQUIRE(acc_flags_stride >= baselines, "acc_flags_stride is smaller than baselines");
-    KSP_REQUIRE(out_vis_stride >= baselines, "out_vis_stride is smaller than baselines");
-    KSP_REQUIRE(out_weights_stride >= baselines, "out_weights_stride is smaller than baselines");
-    KSP_REQUIRE(out_flags_stride >= baselines, "out_flags_stride is smaller than baselines");
-    const int runs_per_row = ksp_divup(baselines, AVG_RUN);
-    const long long runs = (long long)(channels / channel_factor) * runs_per_row;
-    const long long groups = (runs + AVG_THREADS - 1) / AVG_THREADS;
-    KSP_REQUIRE(groups <= 0x7fffffffll, "array too large for one launch");
-    const int aligned =
-        ksp_rows_aligned_if_given(acc_vis, acc_vis_stride, 8) &&
-        ksp_rows_aligned_if_given(acc_weights, acc_weights_stride, 4) &&
-        ksp_rows_aligned_if_given(acc_flags, acc_flags_stride, 1) &&
-        ksp_rows_aligned_if_given(out_vis, out_vis_stride, 8) &&
-        ksp_rows_aligned_if_given(out_weights, out_weights_stride, 4) &&
-        ksp_rows_aligned_if_given(out_flags, out_flags_stride, 1);
+    KSP_TRY(ksp_planes_hold(planes, baselines, "baselines"));
+    ksp_run_grid g;
+    KSP_TRY(ksp_make_run_grid(channels / channel_factor, baselines, AVG_RUN, AVG_THREADS, g));
+    const int aligned = ksp_planes_aligned(planes);
 
     KSP_CHECK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)groups);
-    if (clear)
-        hipLaunchKernelGGL(average_finalise_kernel<true>, grid, dim3(AVG_THREADS), 0, s,
-                           (float2 *)acc_vis, acc_weights, acc_flags, (float2 *)out_vis,
-                           out_weights, out_flags, runs, runs_per_row, baselines, channel_factor,
+    ksp_dispatch_bool(clear != 0, [&](auto CLEAR) {
+        hipLaunchKernelGGL(average_finalise_kernel<CLEAR()>, dim3((unsigned)g.groups),
+                           dim3(AVG_THREADS), 0, (hipStream_t)stream, (float2 *)acc_vis,
+                           acc_weights, acc_flags, (float2 *)out_vis, out_weights, out_flags,
+                           g.runs, g.runs_per_row, baselines, channel_factor,
                            (long long)acc_vis_stride, (long long)acc_weights_stride,
                            (long long)acc_flags_stride, (long long)out_vis_stride,
                            (long long)out_weights_stride, (long long)out_flags_stride, aligned);
-    else
-        hipLaunchKernelGGL(average_finalise_kernel<false>, grid, dim3(AVG_THREADS), 0, s,
-                           (float2 *)acc_vis, acc_weights, acc_flags, (float2 *)out_vis,
-                           out_weights, out_flags, runs, runs_per_row, baselines, channel_factor,
-                           (long long)acc_vis_stride, (long long)acc_weights_stride,
-                           (long long)acc_flags_stride, (long long)out_vis_stride,
-                           (long long)out_weights_stride, (long long)out_flags_stride, aligned);
+    });
     KSP_LAUNCH_CHECK();
     return 0;
 }
+

@@ -203,23 +203,6 @@ void average_accumulate_block_kernel(
     }
 }
 
-template <bool HAS_W>
-static void avgb_launch(int mode, dim3 grid, hipStream_t stream, const avgb_ptrs &p, int n_dumps,
-                        float2 *acc_vis, float *acc_weights, uint8_t *acc_flags, long long runs,
-                        int runs_per_row, int baselines, int vis_stride, int flags_stride,
-                        int weights_stride, int input_flags_stride, int acc_vis_stride,
-                        int acc_weights_stride, int acc_flags_stride, int aligned)
-{
-    // (mode is 0 .. 2 here)
-    ksp_dispatch_exact<0, 1, 2>(mode, [&](auto MODE) {
-        hipLaunchKernelGGL((average_accumulate_block_kernel<HAS_W, MODE()>), grid,
-                           dim3(AVGB_THREADS), 0, stream, p, n_dumps, acc_vis, acc_weights,
-                           acc_flags, runs, runs_per_row, baselines, vis_stride, flags_stride,
-                           weights_stride, input_flags_stride, acc_vis_stride, acc_weights_stride,
-                           acc_flags_stride, aligned);
-    });
-}
-
 extern "C" int ksp_average_accumulate_block(
     int device, void *stream, int n_dumps, const void *const *vis, const uint8_t *const *flags,
     const float *const *weights, const uint8_t *const *input_flags, int input_flags_mode,
@@ -230,9 +213,10 @@ extern "C" int ksp_average_accumulate_block(
     KSP_REQUIRE(n_dumps >= 1 && n_dumps <= AVGB_MAX_DUMPS, "n_dumps must be 1..8");
     KSP_REQUIRE(vis != nullptr, "vis is NULL");
     KSP_REQUIRE(flags != nullptr, "flags is NULL");
-    KSP_REQUIRE(acc_vis != nullptr, "acc_vis is NULL");
-    KSP_REQUIRE(acc_weights != nullptr, "acc_weights is NULL");
-    KSP_REQUIRE(acc_flags != nullptr, "acc_flags is NULL");
+    const ksp_planes acc = {{"acc_vis", acc_vis, acc_vis_stride, 8},
+                            {"acc_weights", acc_weights, acc_weights_stride, 4},
+                            {"acc_flags", acc_flags, acc_flags_stride, 1}};
+    KSP_TRY(ksp_planes_given(acc));
     KSP_REQUIRE(input_flags_mode >= 0 && input_flags_mode <= 2,
                 "input_flags_mode must be 0 (none), 1 (per channel) or 2 (per sample)");
     KSP_REQUIRE(input_flags_mode == 0 || input_flags != nullptr,
@@ -248,50 +232,42 @@ extern "C" int ksp_average_accumulate_block(
     }
     KSP_REQUIRE(channels >= 1, "channels must be at least 1");
     KSP_REQUIRE(baselines >= 1, "baselines must be at least 1");
-    KSP_REQUIRE(vis_stride >= baselines, "vis_stride is smaller than baselines");
-    KSP_REQUIRE(flags_stride >= baselines, "flags_stride is smaller than baselines");
-    KSP_REQUIRE(weights == nullptr || weights_stride >= baselines,
-                "weights_stride is smaller than baselines");
-    KSP_REQUIRE(input_flags_mode != 2 || input_flags_stride >= baselines,
-                "input_flags_stride is smaller than baselines");
-    KSP_REQUIRE(acc_vis_stride >= baselines, "acc_vis_stride is smaller than baselines");
-    KSP_REQUIRE(acc_weights_stride >= baselines, "acc_weights_stride is smaller than baselines");
-    KSP_REQUIRE(acc_flags_stride >= baselines, "acc_flags_stride is smaller than baselines");
-    const int runs_per_row = ksp_divup(baselines, AVGB_RUN);
-    const long long runs = (long long)channels * runs_per_row;
-    const long long groups = (runs + AVGB_THREADS - 1) / AVGB_THREADS;
-    KSP_REQUIRE(groups <= 0x7fffffffll, "array too large for one launch");
-
     // one misaligned pointer of one dump sends the whole call down the element path
     avgb_ptrs p = {};
-    int aligned = ksp_rows_aligned(acc_vis, acc_vis_stride, 8) &&
-                   ksp_rows_aligned(acc_weights, acc_weights_stride, 4) &&
-                   ksp_rows_aligned(acc_flags, acc_flags_stride, 1);
+    int aligned = 1;
     for (int d = 0; d < n_dumps; d++) {
         p.vis[d] = (const float2 *)vis[d];
         p.flags[d] = flags[d];
         p.weights[d] = weights != nullptr ? weights[d] : nullptr;
         p.input_flags[d] = input_flags != nullptr ? input_flags[d] : nullptr;
-        aligned = aligned && ksp_rows_aligned(p.vis[d], vis_stride, 8) &&
-                  ksp_rows_aligned(p.flags[d], flags_stride, 1) &&
-                  ksp_rows_aligned_if_given(p.weights[d], weights_stride, 4) &&
-                  (input_flags_mode != 2 ||
-                   ksp_rows_aligned(p.input_flags[d], input_flags_stride, 1));
+        // (input_flags has a row stride only as one byte per sample)
+        const ksp_planes dump = {
+            {"vis", p.vis[d], vis_stride, 8},
+            {"flags", p.flags[d], flags_stride, 1},
+            {"weights", p.weights[d], weights_stride, 4, true},
+            {"input_flags", input_flags_mode == 2 ? p.input_flags[d] : nullptr,
+             input_flags_stride, 1, true}};
+        KSP_TRY(ksp_planes_hold(dump, baselines, "baselines"));
+        aligned = aligned && ksp_planes_aligned(dump);
     }
+    KSP_TRY(ksp_planes_hold(acc, baselines, "baselines"));
+    aligned = aligned && ksp_planes_aligned(acc);
+    ksp_run_grid g;
+    KSP_TRY(ksp_make_run_grid(channels, baselines, AVGB_RUN, AVGB_THREADS, g));
 
     KSP_CHECK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)groups);
-    if (weights != nullptr)
-        avgb_launch<true>(input_flags_mode, grid, s, p, n_dumps, (float2 *)acc_vis, acc_weights,
-                          acc_flags, runs, runs_per_row, baselines, vis_stride, flags_stride,
-                          weights_stride, input_flags_stride, acc_vis_stride, acc_weights_stride,
-                          acc_flags_stride, aligned);
-    else
-        avgb_launch<false>(input_flags_mode, grid, s, p, n_dumps, (float2 *)acc_vis, acc_weights,
-                           acc_flags, runs, runs_per_row, baselines, vis_stride, flags_stride,
-                           weights_stride, input_flags_stride, acc_vis_stride,
-                           acc_weights_stride, acc_flags_stride, aligned);
+    ksp_dispatch_bool(weights != nullptr, [&](auto HAS_W) {
+        // (input_flags_mode is 0 .. 2 here)
+        ksp_dispatch_exact<0, 1, 2>(input_flags_mode, [&](auto MODE) {
+            hipLaunchKernelGGL(
+                (average_accumulate_block_kernel<decltype(HAS_W)::value, MODE()>),
+                dim3((unsigned)g.groups), dim3(AVGB_THREADS), 0, (hipStream_t)stream, p, n_dumps,
+                (float2 *)acc_vis, acc_weights, acc_flags, g.runs, g.runs_per_row, baselines,
+                vis_stride, flags_stride, weights_stride, input_flags_stride, acc_vis_stride,
+                acc_weights_stride, acc_flags_stride, aligned);
+        });
+    });
     KSP_LAUNCH_CHECK();
     return 0;
 }
+

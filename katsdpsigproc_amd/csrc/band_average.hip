@@ -224,12 +224,16 @@ extern "C" int ksp_band_average(int device, void *stream, const void *data,
                                 int weight_sums_stride, int counts_stride,
                                 int series_flags_stride, int mask)
 {
-    KSP_REQUIRE(data != nullptr, "data is NULL");
-    KSP_REQUIRE(channel_weights != nullptr, "channel_weights is NULL");
-    KSP_REQUIRE(mean != nullptr, "mean is NULL");
-    KSP_REQUIRE(mean_amplitude != nullptr, "mean_amplitude is NULL");
-    KSP_REQUIRE(weight_sums != nullptr, "weight_sums is NULL");
-    KSP_REQUIRE(counts != nullptr, "counts is NULL");
+    const ksp_planes in = {{"data", data, data_stride, 8}, {"flags", flags, flags_stride, 1, true}};
+    const ksp_plane series = {"channel_weights", channel_weights, channel_weights_stride, 4};
+    const ksp_planes out = {{"mean", mean, mean_stride, 8},
+                            {"mean_amplitude", mean_amplitude, mean_amplitude_stride, 4},
+                            {"weight_sums", weight_sums, weight_sums_stride, 4},
+                            {"counts", counts, counts_stride, 4},
+                            {"series_flags", series_flags, series_flags_stride, 1, true}};
+    KSP_TRY(ksp_planes_given(in));
+    KSP_TRY(ksp_planes_given({series}));
+    KSP_TRY(ksp_planes_given(out));
     KSP_REQUIRE(work_area != nullptr, "work_area is NULL");
     KSP_REQUIRE((flags == nullptr) == (series_flags == nullptr),
                 "flags and series_flags must both be NULL or both be given");
@@ -238,18 +242,9 @@ extern "C" int ksp_band_average(int device, void *stream, const void *data,
     KSP_REQUIRE(channels >= 1 && channels <= BA_MAX_CHANNELS, "channels must be 1..262144");
     KSP_REQUIRE(baselines >= 1, "baselines must be at least 1");
     KSP_REQUIRE(n_series >= 1 && n_series <= BA_MAX_SERIES, "n_series must be 1..8");
-    KSP_REQUIRE(data_stride >= baselines, "data_stride is smaller than baselines");
-    KSP_REQUIRE(flags == nullptr || flags_stride >= baselines,
-                "flags_stride is smaller than baselines");
-    KSP_REQUIRE(channel_weights_stride >= channels,
-                "channel_weights_stride is smaller than channels");
-    KSP_REQUIRE(mean_stride >= baselines, "mean_stride is smaller than baselines");
-    KSP_REQUIRE(mean_amplitude_stride >= baselines,
-                "mean_amplitude_stride is smaller than baselines");
-    KSP_REQUIRE(weight_sums_stride >= baselines, "weight_sums_stride is smaller than baselines");
-    KSP_REQUIRE(counts_stride >= baselines, "counts_stride is smaller than baselines");
-    KSP_REQUIRE(series_flags == nullptr || series_flags_stride >= baselines,
-                "series_flags_stride is smaller than baselines");
+    KSP_TRY(ksp_planes_hold(in, baselines, "baselines"));
+    KSP_TRY(ksp_planes_hold({series}, channels, "channels"));
+    KSP_TRY(ksp_planes_hold(out, baselines, "baselines"));
     KSP_REQUIRE((uintptr_t)work_area % sizeof(float) == 0, "work_area is not 4-byte aligned");
     KSP_REQUIRE(work_bytes >= ksp_band_average_work_bytes(channels, baselines, n_series),
                 "work_area is smaller than ksp_band_average_work_bytes");

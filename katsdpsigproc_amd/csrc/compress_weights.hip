@@ -199,15 +199,14 @@ extern "C" int ksp_compress_weights(int device, void *stream, const float *weigh
                                     uint8_t *weights8, float *weights_channel, int channels,
                                     int baselines, int weights_stride, int weights8_stride)
 {
-    KSP_REQUIRE(weights != nullptr, "weights is NULL");
-    KSP_REQUIRE(weights8 != nullptr, "weights8 is NULL");
-    KSP_REQUIRE(weights_channel != nullptr, "weights_channel is NULL");
+    const ksp_plane in = {"weights", weights, weights_stride, 4};
+    const ksp_plane out = {"weights8", weights8, weights8_stride, 1};
+    KSP_TRY(ksp_planes_given({in, out, {"weights_channel", weights_channel, 0, 4}}));
     KSP_REQUIRE(channels >= 1, "channels must be at least 1");
     KSP_REQUIRE(baselines >= 1, "baselines must be at least 1");
-    KSP_REQUIRE(weights_stride >= baselines, "weights_stride is smaller than baselines");
-    KSP_REQUIRE(weights8_stride >= baselines, "weights8_stride is smaller than baselines");
-    const int aligned = (ksp_rows_aligned(weights, weights_stride, 4) ? CW_ALIGNED_LOADS : 0) |
-                        (ksp_rows_aligned(weights8, weights8_stride, 1) ? CW_ALIGNED_STORES : 0);
+    KSP_TRY(ksp_planes_hold({in, out}, baselines, "baselines"));
+    const int aligned = (ksp_planes_aligned({in}) ? CW_ALIGNED_LOADS : 0) |
+                        (ksp_planes_aligned({out}) ? CW_ALIGNED_STORES : 0);
 
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;

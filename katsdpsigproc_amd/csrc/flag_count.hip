@@ -183,24 +183,6 @@ static int fc_tile_rows(int rows, long long col_tiles, int n_masks)
     return (int)(t < lo ? lo : t > FC_MAX_TILE_ROWS ? FC_MAX_TILE_ROWS : t);
 }
 
-template <int NM>
-static void fc_launch(bool single_bit, dim3 grid, hipStream_t stream, const uint8_t *flags,
-                      uint32_t *row_counts, uint32_t *col_counts, int rows, int cols, int stride,
-                      int row_counts_stride, int col_counts_stride, int tile_rows,
-                      unsigned col_tiles, int aligned, const fc_masks &masks)
-{
-    if (single_bit)
-        hipLaunchKernelGGL((flag_count_kernel<NM, true>), grid, dim3(FC_THREADS), 0, stream, flags,
-                           row_counts, col_counts, rows, cols, (long long)stride,
-                           (long long)row_counts_stride, (long long)col_counts_stride, tile_rows,
-                           col_tiles, aligned, masks);
-    else
-        hipLaunchKernelGGL((flag_count_kernel<NM, false>), grid, dim3(FC_THREADS), 0, stream, flags,
-                           row_counts, col_counts, rows, cols, (long long)stride,
-                           (long long)row_counts_stride, (long long)col_counts_stride, tile_rows,
-                           col_tiles, aligned, masks);
-}
-
 extern "C" int ksp_flag_count(int device, void *stream, const uint8_t *flags, uint32_t *row_counts,
                               uint32_t *col_counts, int rows, int cols, int stride,
                               int row_counts_stride, int col_counts_stride, const uint8_t *masks,
@@ -242,9 +224,13 @@ extern "C" int ksp_flag_count(int device, void *stream, const uint8_t *flags, ui
     const dim3 grid((unsigned)tiles);
     // (n_masks is 1 .. FC_MAX_MASKS here)
     ksp_dispatch_exact<1, 2, 3, 4, 5, 6, 7, 8>(n_masks, [&](auto NM) {
-        fc_launch<NM()>(single_bit, grid, s, flags, row_counts, col_counts, rows, cols, stride,
-                        row_counts_stride, col_counts_stride, tile_rows, (unsigned)col_tiles,
-                        aligned, packed);
+        ksp_dispatch_bool(single_bit, [&](auto SINGLE_BIT) {
+            hipLaunchKernelGGL((flag_count_kernel<decltype(NM)::value, SINGLE_BIT()>), grid,
+                               dim3(FC_THREADS), 0, s, flags, row_counts, col_counts, rows, cols,
+                               (long long)stride, (long long)row_counts_stride,
+                               (long long)col_counts_stride, tile_rows, (unsigned)col_tiles,
+                               aligned, packed);
+        });
     });
     KSP_LAUNCH_CHECK();
     return 0;

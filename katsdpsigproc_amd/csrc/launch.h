@@ -1,13 +1,23 @@
-// Host-side launch helpers: a run-time integer as a template argument, the alignment test of
-// the 16-byte load paths, what a launcher does once per device, and the choice between a
-// plain and an event-timed launch. No device code.
+// Host-side launch helpers: a run-time integer or bool as a template argument, the array
+// arguments of a launcher as one list of planes (NULL, stride and the alignment test of the
+// 16-byte load paths, each written once), the grid of the kernels that deal runs to threads,
+// what a launcher does once per device, and the choice between a plain and an event-timed
+// launch. No device code.
 #pragma once
 #include <hip/hip_ext.h>
 
 #include <atomic>
+#include <initializer_list>
 #include <type_traits>
 
 #include "ksp_common.h"
+
+// Returns the code of a helper that failed and has said why with ksp_set_error.
+#define KSP_TRY(expr)              \
+    do {                           \
+        const int _rc = (expr);    \
+        if (_rc != 0) return _rc;  \
+    } while (0)
 
 // A run-time integer as a template argument: f(std::integral_constant<int, V>()) for the V of
 // Vs... that equals `value` (exact), or for the first V that `value` does not exceed (ceil:
@@ -22,6 +32,15 @@ inline bool ksp_dispatch_ceil(int value, F &&f)
 {
     return ((value <= Vs && (f(std::integral_constant<int, Vs>()), true)) || ...);
 }
+// The same for a bool: f(std::true_type()) or f(std::false_type()).
+template <typename F>
+inline void ksp_dispatch_bool(bool value, F &&f)
+{
+    if (value)
+        f(std::true_type());
+    else
+        f(std::false_type());
+}
 
 // Whether rows that start at `ptr` and lie `stride` elements of `elem_bytes` bytes apart can
 // be read in pieces of `bytes` bytes: every row starts on a multiple of `bytes`.
@@ -30,10 +49,67 @@ inline bool ksp_rows_aligned(const void *ptr, long long stride, int elem_bytes, 
     return (uintptr_t)ptr % bytes == 0 && stride * elem_bytes % bytes == 0;
 }
 
-// The same for an optional array: one that is not given (NULL) does not object.
-inline bool ksp_rows_aligned_if_given(const void *ptr, long long stride, int elem_bytes)
+// One [rows][stride] array argument as a launcher's checks see it: its name in the header,
+// the pointer (NULL: not given), the row stride in elements (0 for a one-dimensional array)
+// and the bytes of an element. `optional` arrays may be left out by the caller. A launcher
+// states each array once, in a list in the order of its checks, and hands the list (or part
+// of it) to the three functions below.
+struct ksp_plane {
+    const char *name;
+    const void *ptr;
+    long long stride;
+    int elem_bytes;
+    bool optional = false;
+};
+using ksp_planes = std::initializer_list<ksp_plane>;
+
+// "<name> is NULL" for the first plane that is not given and not optional.
+inline int ksp_planes_given(ksp_planes planes)
 {
-    return ptr == nullptr || ksp_rows_aligned(ptr, stride, elem_bytes);
+    for (const ksp_plane &p : planes)
+        if (p.ptr == nullptr && !p.optional) {
+            ksp_set_error("invalid argument: %s is NULL", p.name);
+            return (int)hipErrorInvalidValue;
+        }
+    return 0;
+}
+
+// "<name>_stride is smaller than <what>" for the first given plane whose rows are shorter
+// than `cols` elements.
+inline int ksp_planes_hold(ksp_planes planes, long long cols, const char *what)
+{
+    for (const ksp_plane &p : planes)
+        if (p.ptr != nullptr && p.stride < cols) {
+            ksp_set_error("invalid argument: %s_stride is smaller than %s", p.name, what);
+            return (int)hipErrorInvalidValue;
+        }
+    return 0;
+}
+
+// Whether every given plane passes ksp_rows_aligned: the kernel may use 16-byte accesses.
+inline bool ksp_planes_aligned(ksp_planes planes)
+{
+    for (const ksp_plane &p : planes)
+        if (p.ptr != nullptr && !ksp_rows_aligned(p.ptr, p.stride, p.elem_bytes)) return false;
+    return true;
+}
+
+// The grid of a kernel whose threads each take a run of `run` adjacent columns of one row,
+// runs numbered row by row: `groups` workgroups of `threads`.
+struct ksp_run_grid {
+    int runs_per_row;
+    long long runs, groups;
+};
+inline int ksp_make_run_grid(long long rows, int cols, int run, int threads, ksp_run_grid &g)
+{
+    g.runs_per_row = (int)(((long long)cols + run - 1) / run);
+    g.runs = rows * g.runs_per_row;
+    g.groups = (g.runs + threads - 1) / threads;
+    if (g.groups > 0x7fffffffll) {
+        ksp_set_error("invalid argument: array too large for one launch");
+        return (int)hipErrorInvalidValue;
+    }
+    return 0;
 }
 
 // One value per device, for what is set up or queried once per device: T() means "not yet".

@@ -9,7 +9,7 @@
 // column are combined in LDS in a fixed tree order, so the result is deterministic
 // (but, like any float32 sum, order-dependent: the reference test allows
 // rtol = 1e-6, test/test_maskedsum.py:67). HBM-bound at 8 bytes per element.
-#include "ksp_common.h"
+#include "launch.h"
 
 #define MS_COLS 16
 #define MS_PHASES 64
@@ -69,14 +69,11 @@ extern "C" int ksp_maskedsum_float(int device, void *stream, const void *in, con
     if (n_cols == 0) return 0;
     KSP_CHECK(hipSetDevice(device));
     dim3 grid(ksp_divup(n_cols, MS_COLS));
-    if (use_amplitudes)
-        hipLaunchKernelGGL(maskedsum_kernel<true>, grid, dim3(MS_COLS * MS_PHASES), 0,
+    ksp_dispatch_bool(use_amplitudes != 0, [&](auto USE_AMP) {
+        hipLaunchKernelGGL(maskedsum_kernel<USE_AMP()>, grid, dim3(MS_COLS * MS_PHASES), 0,
                            (hipStream_t)stream, (const float2 *)in, mask, out, in_stride, n_rows,
                            n_cols);
-    else
-        hipLaunchKernelGGL(maskedsum_kernel<false>, grid, dim3(MS_COLS * MS_PHASES), 0,
-                           (hipStream_t)stream, (const float2 *)in, mask, out, in_stride, n_rows,
-                           n_cols);
+    });
     KSP_LAUNCH_CHECK();
     return 0;
 }

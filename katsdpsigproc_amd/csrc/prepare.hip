@@ -279,10 +279,20 @@ extern "C" int ksp_prepare_flags(int device, void *stream, const int32_t *vis_in
                                  int vis_stride, int input_flags_stride, int weights_stride,
                                  float scale, float weight_scale, int lost_flag)
 {
-    KSP_REQUIRE(vis_in != nullptr, "vis_in is NULL");
-    KSP_REQUIRE(source != nullptr, "source is NULL");
-    KSP_REQUIRE(vis != nullptr, "vis is NULL");
-    KSP_REQUIRE(input_flags != nullptr, "input_flags is NULL");
+    const ksp_plane raw = {"vis_in", vis_in, vis_in_stride, 4};
+    const ksp_planes tables = {{"source", source, 0, 4},
+                               {"auto_source", auto_source, 0, 4, true},
+                               {"mask_index", mask_index, 0, 1, true},
+                               {"baseline_flags", baseline_flags, 0, 1, true}};
+    const ksp_planes out = {{"vis", vis, vis_stride, 8},
+                            {"input_flags", input_flags, input_flags_stride, 1},
+                            {"weights", weights, weights_stride, 4, true}};
+    // (the row stride of channel_flags is looked at only with classes of masks)
+    const ksp_plane masks = {"channel_flags", mask_classes != 0 ? channel_flags : nullptr,
+                             channel_flags_stride, 1, true};
+    KSP_TRY(ksp_planes_given({raw}));
+    KSP_TRY(ksp_planes_given(tables));
+    KSP_TRY(ksp_planes_given(out));
     KSP_REQUIRE((auto_source == nullptr) == (weights == nullptr),
                 "auto_source and weights must both be given or both be NULL");
     KSP_REQUIRE(mask_classes >= 0 && mask_classes <= PREP_MAX_CLASSES,
@@ -294,46 +304,35 @@ extern "C" int ksp_prepare_flags(int device, void *stream, const int32_t *vis_in
     KSP_REQUIRE(channels >= 1, "channels must be at least 1");
     KSP_REQUIRE(in_baselines >= 1, "in_baselines must be at least 1");
     KSP_REQUIRE(baselines >= 1, "baselines must be at least 1");
-    KSP_REQUIRE(vis_in_stride >= in_baselines, "vis_in_stride is smaller than in_baselines");
-    KSP_REQUIRE(mask_classes == 0 || channel_flags_stride >= channels,
-                "channel_flags_stride is smaller than channels");
-    KSP_REQUIRE(vis_stride >= baselines, "vis_stride is smaller than baselines");
-    KSP_REQUIRE(input_flags_stride >= baselines, "input_flags_stride is smaller than baselines");
-    KSP_REQUIRE(weights == nullptr || weights_stride >= baselines,
-                "weights_stride is smaller than baselines");
+    KSP_TRY(ksp_planes_hold({raw}, in_baselines, "in_baselines"));
+    KSP_TRY(ksp_planes_hold({masks}, channels, "channels"));
+    KSP_TRY(ksp_planes_hold(out, baselines, "baselines"));
     KSP_REQUIRE(prep_positive(scale), "scale must be finite and positive");
     KSP_REQUIRE(weights == nullptr || prep_positive(weight_scale),
                 "weight_scale must be finite and positive");
     KSP_REQUIRE(lost_flag >= 1 && lost_flag <= 255, "lost_flag must be 1..255");
-    const int runs_per_row = ksp_divup(baselines, PREP_RUN);
+    // an item is a run of PREP_ROWS rows
     const int rows_per_item = PREP_ROWS(weights != nullptr);
-    const long long row_groups = ((long long)channels + rows_per_item - 1) / rows_per_item;
-    const long long items = row_groups * runs_per_row;
-    const long long groups = (items + PREP_THREADS - 1) / PREP_THREADS;
-    KSP_REQUIRE(groups <= 0x7fffffffll, "array too large for one launch");
+    ksp_run_grid g;
+    KSP_TRY(ksp_make_run_grid(((long long)channels + rows_per_item - 1) / rows_per_item,
+                              baselines, PREP_RUN, PREP_THREADS, g));
+    // (vis_in is read in pairs of words, the tables and the outputs 16 bytes at a time)
     const int aligned =
-        (uintptr_t)vis_in % 8 == 0 && ksp_rows_aligned(source, 0, 4) &&
-        ksp_rows_aligned_if_given(auto_source, 0, 4) &&
-        ksp_rows_aligned_if_given(mask_index, 0, 1) &&
-        ksp_rows_aligned_if_given(baseline_flags, 0, 1) &&
-        ksp_rows_aligned(vis, vis_stride, 8) &&
-        ksp_rows_aligned(input_flags, input_flags_stride, 1) &&
-        ksp_rows_aligned_if_given(weights, weights_stride, 4);
+        (uintptr_t)vis_in % 8 == 0 && ksp_planes_aligned(tables) && ksp_planes_aligned(out);
 
     KSP_CHECK(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)groups);
     // bit 0: channel mask, 1: weights, 2: classes of masks (only with bit 0), 3: baseline flags
     const int variant = (channel_flags != nullptr ? 1 : 0) + (weights != nullptr ? 2 : 0) +
                         (mask_index != nullptr ? 4 : 0) + (baseline_flags != nullptr ? 8 : 0);
     ksp_dispatch_exact<0, 1, 2, 3, 5, 7, 8, 9, 10, 11, 13, 15>(variant, [&](auto V) {
         hipLaunchKernelGGL(
-            (prepare_kernel<(V() & 1) != 0, (V() & 2) != 0, (V() & 4) != 0, (V() & 8) != 0>), grid,
-            dim3(PREP_THREADS), 0, s, (const int *)vis_in, (const int *)source,
-            (const int *)auto_source, channel_flags, (float2 *)vis, input_flags, weights, items,
-            runs_per_row, channels, in_baselines, baselines, (long long)vis_in_stride,
-            (long long)vis_stride, (long long)input_flags_stride, (long long)weights_stride, scale,
-            weight_scale, (unsigned)lost_flag, aligned, mask_index, baseline_flags,
+            (prepare_kernel<(V() & 1) != 0, (V() & 2) != 0, (V() & 4) != 0, (V() & 8) != 0>),
+            dim3((unsigned)g.groups), dim3(PREP_THREADS), 0, (hipStream_t)stream,
+            (const int *)vis_in, (const int *)source, (const int *)auto_source, channel_flags,
+            (float2 *)vis, input_flags, weights, g.runs, g.runs_per_row, channels, in_baselines,
+            baselines, (long long)vis_in_stride, (long long)vis_stride,
+            (long long)input_flags_stride, (long long)weights_stride, scale, weight_scale,
+            (unsigned)lost_flag, aligned, mask_index, baseline_flags,
             (long long)channel_flags_stride, mask_classes);
     });
     KSP_LAUNCH_CHECK();

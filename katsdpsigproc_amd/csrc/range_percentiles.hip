@@ -307,9 +307,15 @@ extern "C" int ksp_range_percentiles(int device, void *stream, const void *in,
                                      int out_stride, int counts_stride, int range_flags_stride,
                                      const int *ranges, int n_ranges, int is_amplitude, int mask)
 {
-    KSP_REQUIRE(in != nullptr, "in is NULL");
+    // (percentiles goes by two names: its row stride is out_stride)
+    const ksp_planes by_baseline = {{"in", in, in_stride, is_amplitude ? 4 : 8},
+                                    {"flags", flags, flags_stride, 1, true}};
+    const ksp_planes by_channel = {{"out", percentiles, out_stride, 4},
+                                   {"counts", counts, counts_stride, 4},
+                                   {"range_flags", range_flags, range_flags_stride, 1, true}};
+    KSP_TRY(ksp_planes_given(by_baseline));
     KSP_REQUIRE(percentiles != nullptr, "percentiles is NULL");
-    KSP_REQUIRE(counts != nullptr, "counts is NULL");
+    KSP_TRY(ksp_planes_given(by_channel));
     KSP_REQUIRE(ranges != nullptr, "ranges is NULL");
     KSP_REQUIRE((flags == nullptr) == (range_flags == nullptr),
                 "flags and range_flags must both be NULL or both be given");
@@ -318,13 +324,8 @@ extern "C" int ksp_range_percentiles(int device, void *stream, const void *in,
     KSP_REQUIRE(channels >= 0, "channels must not be negative");
     KSP_REQUIRE(baselines >= 1, "baselines must be at least 1");
     KSP_REQUIRE(n_ranges >= 1 && n_ranges <= RP_MAX_RANGES, "n_ranges must be 1..16");
-    KSP_REQUIRE(in_stride >= baselines, "in_stride is smaller than baselines");
-    KSP_REQUIRE(flags == nullptr || flags_stride >= baselines,
-                "flags_stride is smaller than baselines");
-    KSP_REQUIRE(out_stride >= channels, "out_stride is smaller than channels");
-    KSP_REQUIRE(counts_stride >= channels, "counts_stride is smaller than channels");
-    KSP_REQUIRE(range_flags == nullptr || range_flags_stride >= channels,
-                "range_flags_stride is smaller than channels");
+    KSP_TRY(ksp_planes_hold(by_baseline, baselines, "baselines"));
+    KSP_TRY(ksp_planes_hold(by_channel, channels, "channels"));
     RpParams p = {};
     for (int r = 0; r < n_ranges; r++) {
         const int start = ranges[2 * r], stop = ranges[2 * r + 1];

@@ -528,22 +528,19 @@ extern "C" int ksp_sir(int device, void *stream, uint8_t *flags, int rows, int c
         ksp_dispatch_ceil<1, 2, 4, 8, SIR0_MAX_LEAVES>(want, [&](auto L) {
             constexpr int panel_rows = per_leaf * L();
             const int panels = (rows + panel_rows - 1) / panel_rows;  // <= SIR0_MAX_PANELS
-            if (pair)
-                hipLaunchKernelGGL((sir_columns_kernel<true, L()>), grid, dim3(SIR0_THREADS), 0, s,
-                                   flags, rows, cols, (long long)stride, panels, par);
-            else
-                hipLaunchKernelGGL((sir_columns_kernel<false, L()>), grid, dim3(SIR0_THREADS), 0, s,
-                                   flags, rows, cols, (long long)stride, panels, par);
+            ksp_dispatch_bool(pair, [&](auto PAIR) {
+                hipLaunchKernelGGL((sir_columns_kernel<PAIR(), decltype(L)::value>), grid,
+                                   dim3(SIR0_THREADS), 0, s, flags, rows, cols, (long long)stride,
+                                   panels, par);
+            });
         });
     } else {
         const int segments = (cols + SIR1_SEGMENT - 1) / SIR1_SEGMENT;  // <= SIR1_MAX_SEGMENTS
         const dim3 grid((unsigned)rows);
-        if (ksp_rows_aligned(flags, stride, 1))
-            hipLaunchKernelGGL(sir_rows_kernel<true>, grid, dim3(SIR1_THREADS), 0, s, flags, cols,
-                               (long long)stride, segments, par);
-        else
-            hipLaunchKernelGGL(sir_rows_kernel<false>, grid, dim3(SIR1_THREADS), 0, s, flags, cols,
-                               (long long)stride, segments, par);
+        ksp_dispatch_bool(ksp_rows_aligned(flags, stride, 1), [&](auto ALIGNED) {
+            hipLaunchKernelGGL(sir_rows_kernel<ALIGNED()>, grid, dim3(SIR1_THREADS), 0, s, flags,
+                               cols, (long long)stride, segments, par);
+        });
     }
     KSP_LAUNCH_CHECK();
     return 0;

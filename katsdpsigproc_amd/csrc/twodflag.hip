@@ -27,6 +27,7 @@
 #include <cmath>
 
 #include "hist_count.h"
+#include "launch.h"
 
 #define TDF_THREADS 256
 
@@ -784,12 +785,10 @@ extern "C" int ksp_twodflag(int device, void *stream, const void *data, const ui
     }
 
     // 1: average
-    if (p->is_amplitude)
-        TDF_LAUNCH(tdf_average<true>, img * nb, data, in_flags, avg, flg, T, F, A, factor, nb, bl0,
-                   (size_t)stride_t, (size_t)stride_f);
-    else
-        TDF_LAUNCH(tdf_average<false>, img * nb, data, in_flags, avg, flg, T, F, A, factor, nb,
+    ksp_dispatch_bool(p->is_amplitude != 0, [&](auto AMP) {
+        TDF_LAUNCH(tdf_average<AMP()>, img * nb, data, in_flags, avg, flg, T, F, A, factor, nb,
                    bl0, (size_t)stride_t, (size_t)stride_f);
+    });
     // 2: spectrum: time median, background, SumThreshold along frequency
     TDF_LAUNCH(tdf_time_median, (size_t)nb * A, avg, flg, spec, specflg, T, A, nb);
     TDF_LAUNCH(tdf_init_work, (size_t)nb * A, specflg, (const uint8_t *)nullptr, specwork, 1, A, nb);
@@ -811,12 +810,10 @@ extern "C" int ksp_twodflag(int device, void *stream, const void *data, const ui
     TDF_LAUNCH(tdf_unavg_rows, (size_t)nb * T, work, rowfl, rowall, T, A, F, nb, factor,
                p->freq_extend, p->flag_all_freq_frac);
     TDF_LAUNCH(tdf_unavg_cols, (size_t)nb * F, rowfl, colall, T, F, nb, p->flag_all_time_frac);
-    if (p->is_amplitude)
-        TDF_LAUNCH(tdf_output<true>, (size_t)T * F * nb, data, rowfl, rowall, colall, out_flags, T,
-                   F, nb, bl0, (size_t)stride_t, (size_t)stride_f);
-    else
-        TDF_LAUNCH(tdf_output<false>, (size_t)T * F * nb, data, rowfl, rowall, colall, out_flags,
+    ksp_dispatch_bool(p->is_amplitude != 0, [&](auto AMP) {
+        TDF_LAUNCH(tdf_output<AMP()>, (size_t)T * F * nb, data, rowfl, rowall, colall, out_flags,
                    T, F, nb, bl0, (size_t)stride_t, (size_t)stride_f);
+    });
     KSP_LAUNCH_CHECK();
     return 0;
 }

@@ -234,7 +234,7 @@ class BackgroundMedianFilterDevice(_native_op.NativeOperation, AbstractBackgroun
         self._launch(
             vis.buffer,
             deviations.buffer,
-            flags.buffer if flags is not None else None,
+            _native_op.pointer(flags),
             np.int32(self.channels),
             np.int32(self.baselines),
             np.int32(vis.padded_shape[1]),
@@ -1437,8 +1437,8 @@ class Accumulate(_native_op.NativeOperation):
         self._launch(
             vis.buffer,
             flags.buffer,
-            weights.buffer if weights is not None else None,
-            in_flags.buffer if in_flags is not None else None,
+            _native_op.pointer(weights),
+            _native_op.pointer(in_flags),
             np.int32(mode.value),
             acc[0].buffer,
             acc[1].buffer,
@@ -1447,7 +1447,7 @@ class Accumulate(_native_op.NativeOperation):
             np.int32(self.baselines),
             np.int32(vis.padded_shape[1]),
             np.int32(flags.padded_shape[1]),
-            np.int32(weights.padded_shape[1] if weights is not None else 0),
+            _native_op.stride(weights),
             np.int32(in_flags.padded_shape[1] if mode == BackgroundFlags.FULL else 0),
             np.int32(acc[0].padded_shape[1]),
             np.int32(acc[1].padded_shape[1]),

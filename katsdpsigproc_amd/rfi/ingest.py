@@ -165,18 +165,18 @@ class Prepare(_native_op.NativeOperation):
         self._launch(
             vis_in.buffer,
             source.buffer,
-            auto_source.buffer if auto_source is not None else None,
-            channel_flags.buffer if channel_flags is not None else None,
+            _native_op.pointer(auto_source),
+            _native_op.pointer(channel_flags),
             vis.buffer,
             input_flags.buffer,
-            weights.buffer if weights is not None else None,
+            _native_op.pointer(weights),
             np.int32(self.channels),
             np.int32(self.in_baselines),
             np.int32(self.baselines),
             np.int32(vis_in.padded_shape[1]),
             np.int32(vis.padded_shape[1]),
             np.int32(input_flags.padded_shape[1]),
-            np.int32(weights.padded_shape[1] if weights is not None else 0),
+            _native_op.stride(weights),
             np.float32(template.scale),
             np.float32(template.weight_scale),
             np.int32(template.lost_flag),
@@ -193,13 +193,13 @@ class Prepare(_native_op.NativeOperation):
         self._launch(
             vis_in.buffer,
             source.buffer,
-            auto_source.buffer if auto_source is not None else None,
-            channel_flags.buffer if channel_flags is not None else None,
-            mask_index.buffer if mask_index is not None else None,
-            baseline_flags.buffer if baseline_flags is not None else None,
+            _native_op.pointer(auto_source),
+            _native_op.pointer(channel_flags),
+            _native_op.pointer(mask_index),
+            _native_op.pointer(baseline_flags),
             vis.buffer,
             input_flags.buffer,
-            weights.buffer if weights is not None else None,
+            _native_op.pointer(weights),
             np.int32(self.channels),
             np.int32(self.in_baselines),
             np.int32(self.baselines),
@@ -208,7 +208,7 @@ class Prepare(_native_op.NativeOperation):
             np.int32(channel_flags.padded_shape[1] if classes >= 1 else 0),
             np.int32(vis.padded_shape[1]),
             np.int32(input_flags.padded_shape[1]),
-            np.int32(weights.padded_shape[1] if weights is not None else 0),
+            _native_op.stride(weights),
             np.float32(template.scale),
             np.float32(template.weight_scale),
             np.int32(template.lost_flag),
@@ -442,23 +442,23 @@ class ApplyGains(_native_op.NativeOperation):
         gains = self.buffer("gains")
         self._launch(
             vis.buffer,
-            weights.buffer if weights is not None else None,
-            flags.buffer if flags is not None else None,
+            _native_op.pointer(weights),
+            _native_op.pointer(flags),
             gains.buffer,
             self.buffer("inputs").buffer,
             out_vis.buffer,
-            out_weights.buffer if out_weights is not None else None,
-            out_flags.buffer if out_flags is not None else None,
+            _native_op.pointer(out_weights),
+            _native_op.pointer(out_flags),
             np.int32(self.channels),
             np.int32(self.baselines),
             np.int32(self.n_inputs),
             np.int32(vis.padded_shape[1]),
-            np.int32(weights.padded_shape[1] if weights is not None else 0),
-            np.int32(flags.padded_shape[1] if flags is not None else 0),
+            _native_op.stride(weights),
+            _native_op.stride(flags),
             np.int32(gains.padded_shape[1]),
             np.int32(out_vis.padded_shape[1]),
-            np.int32(out_weights.padded_shape[1] if out_weights is not None else 0),
-            np.int32(out_flags.padded_shape[1] if out_flags is not None else 0),
+            _native_op.stride(out_weights),
+            _native_op.stride(out_flags),
             np.int32(template.flag_value),
         )
 
@@ -587,17 +587,17 @@ class RangePercentiles(_native_op.NativeOperation):
         range_flags = self.buffer("range_flags") if template.use_flags else None
         self._launch(
             data.buffer,
-            flags.buffer if flags is not None else None,
+            _native_op.pointer(flags),
             percentiles.buffer,
             counts.buffer,
-            range_flags.buffer if range_flags is not None else None,
+            _native_op.pointer(range_flags),
             np.int32(self.channels),
             np.int32(self.baselines),
             np.int32(data.padded_shape[1]),
-            np.int32(flags.padded_shape[1] if flags is not None else 0),
+            _native_op.stride(flags),
             np.int32(percentiles.padded_shape[2]),
             np.int32(counts.padded_shape[1]),
-            np.int32(range_flags.padded_shape[1] if range_flags is not None else 0),
+            _native_op.stride(range_flags),
             self._ranges,
             np.int32(len(self.ranges)),
             np.int32(template.is_amplitude),
@@ -743,26 +743,26 @@ class BandAverage(_native_op.NativeOperation):
         work = self.buffer("work_area")
         self._launch(
             data.buffer,
-            flags.buffer if flags is not None else None,
+            _native_op.pointer(flags),
             weights.buffer,
             mean.buffer,
             amplitude.buffer,
             sums.buffer,
             counts.buffer,
-            series_flags.buffer if series_flags is not None else None,
+            _native_op.pointer(series_flags),
             work.buffer,
             np.uint64(work.shape[0]),
             np.int32(self.channels),
             np.int32(self.baselines),
             np.int32(self.n_series),
             np.int32(data.padded_shape[1]),
-            np.int32(flags.padded_shape[1] if flags is not None else 0),
+            _native_op.stride(flags),
             np.int32(weights.padded_shape[1]),
             np.int32(mean.padded_shape[1]),
             np.int32(amplitude.padded_shape[1]),
             np.int32(sums.padded_shape[1]),
             np.int32(counts.padded_shape[1]),
-            np.int32(series_flags.padded_shape[1] if series_flags is not None else 0),
+            _native_op.stride(series_flags),
             np.int32(template.mask),
         )
 
@@ -913,8 +913,11 @@ class AccumulateBlock(_native_op.NativeOperation):
         return [self.buffer(f"{kind}{d}") for d in range(self._n_dumps)]
 
     @staticmethod
-    def _pointers(buffers: Sequence[accel.DeviceArray]):
-        """The host array of device pointers the launcher reads during the call."""
+    def _pointers(buffers: Optional[Sequence[accel.DeviceArray]]):
+        """The host array of device pointers the launcher reads during the call (None for
+        optional dumps that are absent)."""
+        if buffers is None:
+            return None
         return (ctypes.c_void_p * len(buffers))(*[b.buffer.ptr for b in buffers])
 
     def _run(self) -> None:
@@ -934,8 +937,8 @@ class AccumulateBlock(_native_op.NativeOperation):
             np.int32(self._n_dumps),
             self._pointers(vis),
             self._pointers(flags),
-            self._pointers(weights) if weights is not None else None,
-            self._pointers(in_flags) if in_flags is not None else None,
+            self._pointers(weights),
+            self._pointers(in_flags),
             np.int32(mode.value),
             acc[0].buffer,
             acc[1].buffer,

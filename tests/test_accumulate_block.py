@@ -324,9 +324,9 @@ def test_argument_validation_without_gpu(lib):
         assert "n_dumps must be 1..8" in call(n_dumps=n_dumps, vis=ptrs(*[64] * 9))
     assert "invalid argument: vis is NULL" in call(vis=None)
     assert "invalid argument: flags is NULL" in call(flags=None)
-    assert "acc_vis is NULL" in call(acc_vis=None)
-    assert "acc_weights is NULL" in call(acc_weights=None)
-    assert "acc_flags is NULL" in call(acc_flags=None)
+    assert "invalid argument: acc_vis is NULL" in call(acc_vis=None)
+    assert "invalid argument: acc_weights is NULL" in call(acc_weights=None)
+    assert "invalid argument: acc_flags is NULL" in call(acc_flags=None)
     assert "input_flags is NULL" in call(mode=1)
     assert "input_flags is NULL" in call(mode=2)
     assert "input_flags given" in call(input_flags=ok)
@@ -342,15 +342,25 @@ def test_argument_validation_without_gpu(lib):
     assert "channels" in call(vis=behind, flags=behind, weights=behind, channels=0)
     assert "channels" in call(channels=0)
     assert "baselines" in call(baselines=0)
-    assert "vis_stride" in call(vis_stride=7) and "acc_vis" not in _lib.last_error()
-    assert "flags_stride" in call(flags_stride=7)
-    assert "weights_stride" in call(weights_stride=7)
+    small = "_stride is smaller than baselines"
+    assert "invalid argument: vis" + small in call(vis_stride=7)
+    assert "acc_vis" not in _lib.last_error()
+    assert "invalid argument: flags" + small in call(flags_stride=7)
+    assert "invalid argument: weights" + small in call(weights_stride=7)
     assert "channels" in call(weights=None, weights_stride=7, channels=0)  # (ignored without weights)
-    assert "input_flags_stride" in call(mode=2, input_flags=ok, input_flags_stride=7)
+    assert "invalid argument: input_flags" + small in call(
+        mode=2, input_flags=ok, input_flags_stride=7)  # fmt: skip
     assert "channels" in call(mode=1, input_flags=ok, input_flags_stride=7, channels=0)
-    assert "acc_vis_stride" in call(acc_vis_stride=7)
-    assert "acc_weights_stride" in call(acc_weights_stride=7)
-    assert "acc_flags_stride" in call(acc_flags_stride=7)
+    assert "invalid argument: acc_vis" + small in call(acc_vis_stride=7)
+    assert "invalid argument: acc_weights" + small in call(acc_weights_stride=7)
+    assert "invalid argument: acc_flags" + small in call(acc_flags_stride=7)
+    # the order of the checks: everything wrong at once, then only every stride
+    strides = {name + "_stride": -1 for name in (
+        "vis", "flags", "weights", "input_flags", "acc_vis", "acc_weights", "acc_flags")}  # fmt: skip
+    assert "invalid argument: vis is NULL" in call(
+        vis=None, flags=None, weights=None, acc_vis=None, acc_weights=None, acc_flags=None,
+        channels=0, baselines=0, **strides)  # fmt: skip
+    assert "invalid argument: vis" + small in call(mode=2, input_flags=ok, **strides)
     # 2**31 workgroups of 256 runs of 16 baselines and one more
     assert "too large" in call(channels=2**31 - 1, baselines=2**31 - 1, vis_stride=2**31 - 1,
                                flags_stride=2**31 - 1, weights_stride=2**31 - 1,

@@ -481,6 +481,14 @@ def test_argument_validation_without_gpu(lib):
             **{name + "_stride": 7})
     assert "invalid argument: gains_stride is smaller than n_inputs" in call(gains_stride=2)
     assert "gains_stride is smaller" in call(n_inputs=4096, gains_stride=4095)
+    # the order of the checks: everything wrong at once, then only every stride
+    strides = {name + "_stride": -1 for name in (
+        "vis", "weights", "flags", "gains", "out_vis", "out_weights", "out_flags")}  # fmt: skip
+    assert "invalid argument: vis is NULL" in call(
+        channels=0, baselines=0, n_inputs=0, flag_value=0, **dict.fromkeys(p), **strides)
+    assert "invalid argument: vis_stride is smaller than baselines" in call(**strides)
+    assert "invalid argument: gains_stride is smaller than n_inputs" in call(
+        **dict(strides, vis_stride=8, out_vis_stride=8))  # fmt: skip
     # an absent pair's strides are not looked at: the call gets as far as the next check
     none_w = dict(weights=None, out_weights=None, weights_stride=0, out_weights_stride=0)
     none_f = dict(flags=None, out_flags=None, flags_stride=0, out_flags_stride=0)

@@ -364,11 +364,12 @@ def test_accumulate_argument_validation_without_gpu(lib):
         assert rc != 0
         return _lib.last_error()
 
-    assert "vis is NULL" in call(vis=None) and "acc_vis" not in _lib.last_error()
-    assert "flags is NULL" in call(flags=None)
-    assert "acc_vis is NULL" in call(acc_vis=None)
-    assert "acc_weights is NULL" in call(acc_weights=None)
-    assert "acc_flags is NULL" in call(acc_flags=None)
+    small = "_stride is smaller than baselines"
+    assert "invalid argument: vis is NULL" in call(vis=None) and "acc_vis" not in _lib.last_error()
+    assert "invalid argument: flags is NULL" in call(flags=None)
+    assert "invalid argument: acc_vis is NULL" in call(acc_vis=None)
+    assert "invalid argument: acc_weights is NULL" in call(acc_weights=None)
+    assert "invalid argument: acc_flags is NULL" in call(acc_flags=None)
     assert "input_flags is NULL" in call(mode=1)
     assert "input_flags is NULL" in call(mode=2)
     assert "input_flags given" in call(input_flags=p)
@@ -376,13 +377,22 @@ def test_accumulate_argument_validation_without_gpu(lib):
     assert "input_flags_mode" in call(mode=-1, input_flags=p)
     assert "channels" in call(channels=0)
     assert "baselines" in call(baselines=0)
-    assert "vis_stride" in call(vis_stride=7) and "acc_vis" not in _lib.last_error()
-    assert "flags_stride" in call(flags_stride=7)
-    assert "weights_stride" in call(weights_stride=7)
-    assert "input_flags_stride" in call(mode=2, input_flags=p, input_flags_stride=7)
-    assert "acc_vis_stride" in call(acc_vis_stride=7)
-    assert "acc_weights_stride" in call(acc_weights_stride=7)
-    assert "acc_flags_stride" in call(acc_flags_stride=7)
+    assert "invalid argument: vis" + small in call(vis_stride=7)
+    assert "acc_vis" not in _lib.last_error()
+    assert "invalid argument: flags" + small in call(flags_stride=7)
+    assert "invalid argument: weights" + small in call(weights_stride=7)
+    assert "invalid argument: input_flags" + small in call(
+        mode=2, input_flags=p, input_flags_stride=7)  # fmt: skip
+    assert "invalid argument: acc_vis" + small in call(acc_vis_stride=7)
+    assert "invalid argument: acc_weights" + small in call(acc_weights_stride=7)
+    assert "invalid argument: acc_flags" + small in call(acc_flags_stride=7)
+    # the order of the checks: everything wrong at once, then only every stride
+    strides = {name + "_stride": -1 for name in (
+        "vis", "flags", "weights", "input_flags", "acc_vis", "acc_weights", "acc_flags")}  # fmt: skip
+    assert "invalid argument: vis is NULL" in call(
+        vis=None, flags=None, weights=None, acc_vis=None, acc_weights=None, acc_flags=None,
+        channels=0, baselines=0, **strides)  # fmt: skip
+    assert "invalid argument: vis" + small in call(mode=2, input_flags=p, **strides)
 
 
 def test_finalise_argument_validation_without_gpu(lib):
@@ -403,8 +413,15 @@ def test_finalise_argument_validation_without_gpu(lib):
 
     for name in ("acc_vis", "acc_weights", "acc_flags", "out_vis", "out_weights", "out_flags"):
         assert f"invalid argument: {name} is NULL" in call(**{name: None})
-        assert f"invalid argument: {name}_stride" in call(**{name + "_stride": 7})
+        assert f"invalid argument: {name}_stride is smaller than baselines" in call(
+            **{name + "_stride": 7})  # fmt: skip
     assert "channels" in call(channels=0)
     assert "baselines" in call(baselines=0)
     assert "channel_factor must be" in call(channel_factor=0)
     assert "channel_factor does not divide" in call(channel_factor=3)
+    # the order of the checks: everything wrong at once, then only every stride
+    names = ("acc_vis", "acc_weights", "acc_flags", "out_vis", "out_weights", "out_flags")
+    strides = {name + "_stride": -1 for name in names}
+    assert "invalid argument: acc_vis is NULL" in call(
+        **dict.fromkeys(names), channels=0, baselines=0, channel_factor=0, **strides)
+    assert "invalid argument: acc_vis_stride is smaller than baselines" in call(**strides)

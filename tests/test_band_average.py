@@ -408,6 +408,14 @@ def test_argument_validation_without_gpu(lib):
             **{name + "_stride": 7})  # fmt: skip
     assert "invalid argument: channel_weights_stride is smaller than channels" in call(
         channel_weights_stride=299)  # fmt: skip
+    # the order of the checks: everything wrong at once, then only every stride
+    strides = {name + "_stride": -1 for name in names[:-1]}
+    assert "invalid argument: data is NULL" in call(
+        channels=0, baselines=0, n_series=0, work_bytes=0, mask=-1, **dict.fromkeys(names),
+        **strides)  # fmt: skip
+    assert "invalid argument: data_stride is smaller than baselines" in call(**strides)
+    assert "invalid argument: channel_weights_stride is smaller than channels" in call(
+        **dict(strides, data_stride=8, flags_stride=8))  # fmt: skip
     assert "invalid argument: work_area is not 4-byte aligned" in call(
         work_area=ctypes.c_void_p(66))  # fmt: skip
     small = "invalid argument: work_area is smaller than ksp_band_average_work_bytes"

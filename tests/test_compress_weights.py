@@ -306,3 +306,9 @@ def test_argument_validation_without_gpu(lib):
     assert "invalid argument: weights8_stride is smaller than baselines" in call(weights8_stride=7)
     assert "weights8_stride is smaller" in call(baselines=70000, weights_stride=70000,
                                                 weights8_stride=69999)  # fmt: skip
+    # the order of the checks: everything wrong at once, then only every stride
+    assert "invalid argument: weights is NULL" in call(
+        weights=None, weights8=None, weights_channel=None, channels=0, baselines=0,
+        weights_stride=-1, weights8_stride=-1)  # fmt: skip
+    assert "invalid argument: weights_stride is smaller than baselines" in call(
+        weights_stride=7, weights8_stride=7)  # fmt: skip

@@ -161,15 +161,15 @@ def test_argument_validation_without_gpu(lib):
         assert rc != 0
         return _lib.last_error()
 
-    assert "flags is NULL" in call(flags=None)
-    assert "row_counts is NULL" in call(row_counts=None)
-    assert "col_counts is NULL" in call(col_counts=None)
-    assert "masks is NULL" in call(masks=None)
+    assert "invalid argument: flags is NULL" in call(flags=None)
+    assert "invalid argument: row_counts is NULL" in call(row_counts=None)
+    assert "invalid argument: col_counts is NULL" in call(col_counts=None)
+    assert "invalid argument: masks is NULL" in call(masks=None)
     assert "rows" in call(rows=0)
     assert "cols" in call(cols=0)
-    assert "stride" in call(stride=7) and "cols" in _lib.last_error()
-    assert "row_counts_stride" in call(rstride=3)
-    assert "col_counts_stride" in call(cstride=7)
+    assert "invalid argument: stride is smaller than cols" in call(stride=7)
+    assert "invalid argument: row_counts_stride is smaller than rows" in call(rstride=3)
+    assert "invalid argument: col_counts_stride is smaller than cols" in call(cstride=7)
     assert "n_masks" in call(n_masks=0)
     assert "n_masks" in call(n_masks=9)
     assert "mask is zero" in call(masks=(ctypes.c_uint8 * 2)(1, 0), n_masks=2)

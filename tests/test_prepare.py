@@ -460,10 +460,16 @@ def test_argument_validation_without_gpu(lib):
     assert "channels must be" in call(channels=0)
     assert "in_baselines must be" in call(in_baselines=0)
     assert "invalid argument: baselines must be" in call(baselines=0)
-    assert "vis_in_stride is smaller" in call(vis_in_stride=7)
-    assert "invalid argument: vis_stride is smaller" in call(vis_stride=7)
-    assert "input_flags_stride is smaller" in call(input_flags_stride=7)
-    assert "weights_stride is smaller" in call(weights_stride=7)
+    assert "invalid argument: vis_in_stride is smaller than in_baselines" in call(vis_in_stride=7)
+    for name in ("vis", "input_flags", "weights"):
+        assert f"invalid argument: {name}_stride is smaller than baselines" in call(
+            **{name + "_stride": 7})  # fmt: skip
+    # the order of the checks: everything wrong at once, then only every stride
+    strides = dict(vis_in_stride=-1, vis_stride=-1, input_flags_stride=-1, weights_stride=-1)
+    assert "invalid argument: vis_in is NULL" in call(
+        vis_in=None, source=None, auto_source=None, channel_flags=None, vis=None,
+        input_flags=None, weights=None, channels=0, in_baselines=0, baselines=0, **strides)  # fmt: skip
+    assert "invalid argument: vis_in_stride is smaller than in_baselines" in call(**strides)
     for bad in (0.0, -1.0, float("nan"), float("inf")):
         assert "invalid argument: scale must be finite" in call(scale=bad)
         assert "weight_scale must be finite" in call(weight_scale=bad)

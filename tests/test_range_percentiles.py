@@ -360,6 +360,15 @@ def test_argument_validation_without_gpu(lib):
     assert "invalid argument: counts_stride is smaller than channels" in call(counts_stride=3)
     assert "invalid argument: range_flags_stride is smaller than channels" in call(
         range_flags_stride=3)  # fmt: skip
+    # the order of the checks: everything wrong at once, then only every stride
+    strides = dict(in_stride=-1, flags_stride=-1, out_stride=-1, counts_stride=-1,
+                   range_flags_stride=-1)  # fmt: skip
+    assert "invalid argument: in is NULL" in call(
+        data=None, flags=None, percentiles=None, counts=None, range_flags=None, channels=-1,
+        baselines=0, ranges=None, n_ranges=0, mask=-1, **strides)  # fmt: skip
+    assert "invalid argument: in_stride is smaller than baselines" in call(**strides)
+    assert "invalid argument: out_stride is smaller than channels" in call(
+        **dict(strides, in_stride=8, flags_stride=8))  # fmt: skip
     inside = "invalid argument: a range must satisfy 0 <= start <= stop <= baselines"
     for bad in [(-1, 4), (5, 4), (0, 9), (9, 9)]:
         assert inside in call(ranges=(0, 8) + bad)
