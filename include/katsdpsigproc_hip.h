@@ -575,6 +575,42 @@ int ksp_apply_gains(int device, void *stream, const void *vis, const float *weig
                     int flags_stride, int gains_stride, int out_vis_stride,
                     int out_weights_stride, int out_flags_stride, int flag_value);
 
+/* solve_gains: per-input complex gains solved per channel from averaged visibilities of a point
+ * source at the phase centre, with StEFCal, in one launch (no reference counterpart; bit for bit
+ * what rfi/host.py SolveGainsHost computes, whose docstring states every step; every float step
+ * is one float32 operation, rounded once, a multiply then an add, never an fma; sums run in
+ * blocks of 32 indices, ascending from +0, the block sums added in ascending order).
+ * vis: complex64 [channels][vis_stride]; weights: float32, flags: uint8, same layout, each NULL
+ * or given (w = 1 without weights); pairs: int32 [n_inputs][pairs_stride], of which only the
+ * entries [p][q] with p < q are read: t > 0 is baseline t - 1 listed as (p, q), t < 0 is
+ * baseline -t - 1 listed as (q, p), whose sample is conjugated, and 0 or |t| > baselines (any
+ * int32, INT32_MIN included) is no baseline and forms no address; initial: complex64
+ * [channels][initial_stride] or NULL (1 + 0j); gains: complex64 [channels][gains_stride];
+ * iterations: int32 [channels]; status: uint8 [channels]. Strides in elements.
+ * A sample is kept when its entry is valid, neither part of v is NaN, w > 0 and
+ * (flags & mask) == 0. Per channel, k = 1 .. max_iterations:
+ *   new[p] = sum_q A[p][q] g[q] / sum_q W[p][q] |g[q]|^2  (g[p] where the divisor is not > 0);
+ *   k odd: g = new;  k even: g = (new + g) / 2, and the channel stops, converged, when
+ *   sum_p |g[p] - old[p]|^2 <= tol2 * sum_p |g[p]|^2 over the inputs that have data.
+ * Then, if reference >= 0, that input has data and its gain's magnitude m is positive and
+ * finite, every gain is multiplied by conj(g[reference]) / m and the reference's imaginary part
+ * becomes +0; with corrections != 0 the output is conj(g) / |g|^2 (NaN where |g|^2 is not > 0):
+ * what ksp_apply_gains multiplies by; an input without data gets NaN + NaN j.
+ * iterations[c] is the number of iterations run; status[c] has bit 0 for "not converged",
+ * bit 1 for "no input has data", bit 2 for "not referenced" (reference == -1 included).
+ * tol2 is the square of the relative tolerance, at least 0. n_inputs is 1..128, max_iterations
+ * 1..1000, reference -1..n_inputs-1, mask 0..255, corrections 0 or 1, channels and baselines
+ * at least 1. gains may be initial (the same pointer with the same stride); otherwise it must
+ * share no byte with it. Elements between baselines (or n_inputs) and a stride are neither
+ * read nor written. One workgroup per channel with the channel's matrix in LDS; one kernel
+ * launch, no workspace, no atomics. Every argument is checked before any device call. */
+int ksp_solve_gains(int device, void *stream, const void *vis, const float *weights,
+                    const uint8_t *flags, const int32_t *pairs, const void *initial, void *gains,
+                    int32_t *iterations, uint8_t *status, int channels, int baselines,
+                    int n_inputs, int vis_stride, int weights_stride, int flags_stride,
+                    int pairs_stride, int initial_stride, int gains_stride, int max_iterations,
+                    float tol2, int reference, int mask, int corrections);
+
 /* range_percentiles: per channel and per range of baselines, the [0, 100, 25, 75, 50] %
  * amplitudes ("lower" element) of the samples that are neither NaN nor flagged under a mask,
  * how many those are, and the OR of the range's flags, all ranges in one launch (no reference

@@ -189,17 +189,6 @@ __global__ __launch_bounds__(AG_THREADS) void apply_gains_kernel(
     }
 }
 
-// Whether `out` is `in` itself (same pointer, same stride) or shares no byte with it
-static bool ag_same_or_apart(const void *in, long long in_stride, const void *out,
-                             long long out_stride, int channels, int baselines, int elem_bytes)
-{
-    if (in == out && in_stride == out_stride) return true;
-    const uintptr_t a0 = (uintptr_t)in, b0 = (uintptr_t)out;
-    const uintptr_t a1 = a0 + (uintptr_t)(((channels - 1ll) * in_stride + baselines) * elem_bytes);
-    const uintptr_t b1 = b0 + (uintptr_t)(((channels - 1ll) * out_stride + baselines) * elem_bytes);
-    return a1 <= b0 || b1 <= a0;
-}
-
 extern "C" int ksp_apply_gains(int device, void *stream, const void *vis, const float *weights,
                                const uint8_t *flags, const void *gains, const int32_t *inputs,
                                void *out_vis, float *out_weights, uint8_t *out_flags,
@@ -226,14 +215,15 @@ extern "C" int ksp_apply_gains(int device, void *stream, const void *vis, const 
     KSP_TRY(ksp_planes_hold({in, out}, baselines, "baselines"));
     KSP_TRY(ksp_planes_hold({table}, n_inputs, "n_inputs"));
     KSP_TRY(ksp_planes_hold(pairs, baselines, "baselines"));
-    KSP_REQUIRE(ag_same_or_apart(vis, vis_stride, out_vis, out_vis_stride, channels, baselines, 8),
-                "out_vis overlaps vis without being vis with the same stride");
+    KSP_REQUIRE(
+        ksp_same_or_apart(vis, vis_stride, out_vis, out_vis_stride, channels, baselines, 8),
+        "out_vis overlaps vis without being vis with the same stride");
     KSP_REQUIRE(weights == nullptr ||
-                    ag_same_or_apart(weights, weights_stride, out_weights, out_weights_stride,
-                                     channels, baselines, 4),
+                    ksp_same_or_apart(weights, weights_stride, out_weights, out_weights_stride,
+                                      channels, baselines, 4),
                 "out_weights overlaps weights without being weights with the same stride");
-    KSP_REQUIRE(flags == nullptr || ag_same_or_apart(flags, flags_stride, out_flags,
-                                                     out_flags_stride, channels, baselines, 1),
+    KSP_REQUIRE(flags == nullptr || ksp_same_or_apart(flags, flags_stride, out_flags,
+                                                      out_flags_stride, channels, baselines, 1),
                 "out_flags overlaps flags without being flags with the same stride");
     const ag_geometry geom = ag_make_geometry(channels, baselines);
     KSP_REQUIRE(geom.groups <= 0x7fffffffll, "array too large for one launch");

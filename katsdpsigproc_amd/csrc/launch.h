@@ -1,8 +1,8 @@
 // Host-side launch helpers: a run-time integer or bool as a template argument, the array
 // arguments of a launcher as one list of planes (NULL, stride and the alignment test of the
-// 16-byte load paths, each written once), the grid of the kernels that deal runs to threads,
-// what a launcher does once per device, and the choice between a plain and an event-timed
-// launch. No device code.
+// 16-byte load paths, each written once), the test of an output that may be its input, the
+// grid of the kernels that deal runs to threads, what a launcher does once per device, and the
+// choice between a plain and an event-timed launch. No device code.
 #pragma once
 #include <hip/hip_ext.h>
 
@@ -92,6 +92,18 @@ inline bool ksp_planes_aligned(ksp_planes planes)
     for (const ksp_plane &p : planes)
         if (p.ptr != nullptr && !ksp_rows_aligned(p.ptr, p.stride, p.elem_bytes)) return false;
     return true;
+}
+
+// Whether the [rows][stride] array `out` is `in` itself (same pointer, same stride: in place) or
+// shares no byte with it; `cols` elements of `elem_bytes` bytes per row are data.
+inline bool ksp_same_or_apart(const void *in, long long in_stride, const void *out,
+                              long long out_stride, int rows, int cols, int elem_bytes)
+{
+    if (in == out && in_stride == out_stride) return true;
+    const uintptr_t a0 = (uintptr_t)in, b0 = (uintptr_t)out;
+    const uintptr_t a1 = a0 + (uintptr_t)(((rows - 1ll) * in_stride + cols) * elem_bytes);
+    const uintptr_t b1 = b0 + (uintptr_t)(((rows - 1ll) * out_stride + cols) * elem_bytes);
+    return a1 <= b0 || b1 <= a0;
 }
 
 // The grid of a kernel whose threads each take a run of `run` adjacent columns of one row,

@@ -722,6 +722,269 @@ class ApplyGainsHost:
         return out_vis, out_weights, out_flags
 
 
+class SolveGainsHost:
+    """Per-input complex gains solved from averaged visibilities of a point source at the phase
+    centre, channel by channel, with StEFCal (Salvini & Wijnholds 2014): what produces the
+    gains that :class:`ApplyGainsHost` applies. No reference counterpart; this class is the
+    definition that the device operation (:class:`.ingest.SolveGainsTemplate`) matches bit for
+    bit.
+
+    ``pairs[p, q]`` (only ``p < q`` is read) says where the baseline of inputs ``p`` and ``q``
+    is: ``t > 0`` is baseline ``t - 1`` listed as ``(p, q)``, ``t < 0`` is baseline ``-t - 1``
+    listed as ``(q, p)``, whose sample is conjugated, and ``0`` or ``|t| > baselines`` (any int32)
+    is no baseline; :meth:`pair_table` builds it. A sample is *kept* when its entry is valid,
+    neither part of ``v`` is NaN, ``w > 0`` (1 without `weights`) and ``flags & mask == 0``. Per
+    channel a kept sample stores ``W[p][q] = W[q][p] = w``, ``A[p][q] = (w*v.re, w*v.im)``, the
+    imaginary part negated for ``t < 0``, and ``A[q][p] = conj(A[p][q])``; everything else, the
+    diagonal included, is +0. An input *has data* if its row of ``W`` has a positive entry.
+
+    Every float step is one float32 operation, rounded once (a multiply, then an add, never an
+    fma; real and imaginary parts apart; correctly rounded division and square root). From
+    ``g = initial`` (or 1+0j), for ``k = 1 .. max_iterations``::
+
+        s[q]   = g[q].re*g[q].re + g[q].im*g[q].im
+        num[p] = sum_q (A.re*g.re - A.im*g.im, A.re*g.im + A.im*g.re)     (A = A[p][q], g = g[q])
+        den[p] = sum_q W[p][q]*s[q]
+        new[p] = den[p] > 0 ? (num.re/den, num.im/den) : g[p]
+        k odd : g = new
+        k even: g = ((new.re+g.re)*0.5, (new.im+g.im)*0.5)
+                d = sum_p |g[p]-old[p]|^2,  n = sum_p |g[p]|^2      over the inputs that have data
+                stop, converged, when d <= float32(tol*tol) * n
+
+    with ``|x|^2 = x.re*x.re + x.im*x.im``. Every sum over q or p runs in blocks of
+    :attr:`BLOCK` = 32 indices: within a block sequentially and ascending from +0, and the block
+    sums are then added in ascending order. After the loop:
+
+    * Referencing. If ``reference >= 0``, that input has data and ``m = sqrt(re*re + im*im)``
+      of its gain is positive and finite, every gain is multiplied by ``(re/m, -im/m)`` and the
+      reference's imaginary part is set to +0. Otherwise (``reference=-1`` included) status bit
+      2 is set and the gains stay as they are.
+    * With `corrections` the output is ``(g.re/s, -g.im/s)`` where ``s = |g|^2 > 0``, else NaN:
+      what :class:`ApplyGainsHost` multiplies by.
+    * An input without data comes out as NaN+NaNj, so that :class:`ApplyGainsHost` flags it.
+
+    ``status`` bits: 1 not converged, 2 no input has data, 4 not referenced. Infinities go
+    through as IEEE gives them, and a NaN criterion is "not converged".
+
+    Parameters
+    ----------
+    max_iterations
+        1..1000
+    tol
+        Relative change below which a channel stops, at least 0
+    reference
+        -1 (none) or the input whose gain is made real and positive
+    mask
+        Flag bits that exclude a sample, 0..255 (:func:`check_mask_byte`)
+    corrections
+        ``True``: return the reciprocal gains
+    """
+
+    MAX_INPUTS = 128
+    MAX_ITERATIONS = 1000
+    BLOCK = 32
+    NOT_CONVERGED, NO_DATA, NOT_REFERENCED = 1, 2, 4
+    _CHUNK = 32  # channels worked on at once (memory only)
+
+    def __init__(self, max_iterations: int = 30, tol: float = 1e-5, reference: int = 0,
+                 mask: int = 0xFF, corrections: bool = False) -> None:  # fmt: skip
+        for name, value in (("max_iterations", max_iterations), ("reference", reference)):
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+                raise TypeError(f"{name} {value!r} is not an integer")
+        if not 1 <= max_iterations <= self.MAX_ITERATIONS:
+            raise ValueError(f"max_iterations must be 1..{self.MAX_ITERATIONS}")
+        if not float(tol) >= 0:
+            raise ValueError(f"tol {tol!r} must be at least 0")
+        if not -1 <= reference < self.MAX_INPUTS:
+            raise ValueError(f"reference must be -1..{self.MAX_INPUTS - 1}")
+        self.max_iterations = int(max_iterations)
+        self.tol = float(tol)
+        with np.errstate(all="ignore"):
+            self.tol2 = np.float32(self.tol * self.tol)
+        self.reference = int(reference)
+        self.mask = check_mask_byte("mask", mask)
+        self.corrections = bool(corrections)
+
+    @classmethod
+    def check_n_inputs(cls, n_inputs) -> int:
+        """`n_inputs` as an int in 1..128 (``ValueError`` otherwise, ``TypeError`` for a value
+        that is not an integer)."""
+        if isinstance(n_inputs, (bool, np.bool_)) or not isinstance(n_inputs, (int, np.integer)):
+            raise TypeError(f"n_inputs {n_inputs!r} is not an integer")
+        if not 1 <= n_inputs <= cls.MAX_INPUTS:
+            raise ValueError(f"n_inputs must be 1..{cls.MAX_INPUTS}")
+        return int(n_inputs)
+
+    @classmethod
+    def pair_table(cls, inputs, n_inputs: int) -> np.ndarray:
+        """The int32 (n_inputs, n_inputs) table of `inputs` (baselines x 2, as
+        :class:`ApplyGainsHost` takes them). Autocorrelations and baselines with an entry
+        outside ``0..n_inputs-1`` take no part; ``ValueError`` for a pair that is listed twice,
+        in either order."""
+        n_inputs = cls.check_n_inputs(n_inputs)
+        inputs = np.asarray(inputs)
+        if inputs.ndim != 2 or inputs.shape[1] != 2 or inputs.dtype.kind not in "iu":
+            raise ValueError(f"inputs must be integers of shape (baselines, 2), not "
+                             f"{inputs.dtype.name} {inputs.shape}")  # fmt: skip
+        if len(inputs) >= 2**31:
+            raise ValueError("inputs lists more than 2^31 - 1 baselines")
+        table = np.zeros((n_inputs, n_inputs), np.int32)
+        for j, (a, b) in enumerate(inputs.tolist()):
+            if a == b or not (0 <= a < n_inputs and 0 <= b < n_inputs):
+                continue
+            p, q, entry = (a, b, j + 1) if a < b else (b, a, -(j + 1))
+            if table[p, q] != 0:
+                raise ValueError(f"inputs lists the pair ({p}, {q}) twice: baselines "
+                                 f"{abs(int(table[p, q])) - 1} and {j}")  # fmt: skip
+            table[p, q] = entry
+        return table
+
+    @classmethod
+    def _block_sum(cls, terms: np.ndarray) -> np.ndarray:
+        """float32 sums over the last axis in the order of the class docstring."""
+        total = None
+        for start in range(0, terms.shape[-1], cls.BLOCK):
+            partial = np.zeros(terms.shape[:-1], np.float32)
+            for i in range(start, min(start + cls.BLOCK, terms.shape[-1])):
+                partial = partial + terms[..., i]
+            total = partial if total is None else total + partial
+        assert total.dtype == np.float32
+        return total
+
+    def __call__(self, vis: np.ndarray, pairs: np.ndarray, weights: Optional[np.ndarray] = None,
+                 flags: Optional[np.ndarray] = None, initial: Optional[np.ndarray] = None):  # fmt: skip
+        """``(gains, iterations, status)``: complex64 (channels, n_inputs), int32 (channels,)
+        and uint8 (channels,), for complex64 `vis` (channels, baselines), int32 `pairs`
+        (n_inputs, n_inputs), optional float32 `weights`, optional uint8 `flags` (both channels,
+        baselines) and optional complex64 `initial` (channels, n_inputs). ``ValueError``, naming
+        the argument, for a wrong dtype, rank or shape (channels and baselines at least 1,
+        n_inputs 1..128) and for a `reference` that is not below n_inputs. No argument is
+        modified."""
+        vis = _check_array("vis", vis, np.complex64, "(channels, baselines)",
+                           lambda s: len(s) == 2 and s[0] >= 1 and s[1] >= 1)  # fmt: skip
+        channels, baselines = vis.shape
+        pairs = _check_array("pairs", pairs, np.int32, "(n_inputs, n_inputs), n_inputs 1..128",
+                             lambda s: len(s) == 2 and s[0] == s[1]
+                             and 1 <= s[0] <= self.MAX_INPUTS)  # fmt: skip
+        n = pairs.shape[0]
+        if weights is not None:
+            weights = _check_array("weights", weights, np.float32, "(channels, baselines)",
+                                   lambda s: s == vis.shape)  # fmt: skip
+        if flags is not None:
+            flags = _check_array("flags", flags, np.uint8, "(channels, baselines)",
+                                 lambda s: s == vis.shape)  # fmt: skip
+        if initial is not None:
+            initial = _check_array("initial", initial, np.complex64, "(channels, n_inputs)",
+                                   lambda s: s == (channels, n))  # fmt: skip
+        if self.reference >= n:
+            raise ValueError(f"reference must be -1 or 0..n_inputs-1 = {n - 1}, not {self.reference}")
+        gains = np.empty((channels, n), np.complex64)
+        iterations = np.empty(channels, np.int32)
+        status = np.empty(channels, np.uint8)
+        for c0 in range(0, channels, self._CHUNK):
+            rows = slice(c0, min(c0 + self._CHUNK, channels))
+            gains[rows], iterations[rows], status[rows] = self._solve(
+                vis[rows], pairs, None if weights is None else weights[rows],
+                None if flags is None else flags[rows],
+                None if initial is None else initial[rows])  # fmt: skip
+        return gains, iterations, status
+
+    def _matrix(self, vis, pairs, weights, flags):
+        """``A.re, A.im, W`` (channels, n, n) float32 of the class docstring."""
+        channels, baselines = vis.shape
+        n = pairs.shape[0]
+        f32 = np.float32
+        p, q = np.triu_indices(n, 1)
+        t = pairs[p, q].astype(np.int64)
+        valid = (t != 0) & (np.abs(t) <= baselines)
+        j = np.where(valid, np.abs(t) - 1, 0)
+        v = vis[:, j]
+        w = np.ones(v.shape, f32) if weights is None else weights[:, j]
+        kept = valid[np.newaxis, :] & ~np.isnan(v.real) & ~np.isnan(v.imag) & (w > 0)
+        if flags is not None:
+            kept &= (flags[:, j] & np.uint8(self.mask)) == 0
+        zero = f32(0)
+        a_im = w * v.imag
+        a_im = np.where(kept, np.where(t < 0, -a_im, a_im), zero)
+        a_re = np.where(kept, w * v.real, zero)
+        big_re, big_im, big_w = (np.zeros((channels, n, n), f32) for _ in range(3))
+        big_re[:, p, q] = a_re
+        big_re[:, q, p] = a_re
+        big_im[:, p, q] = a_im
+        big_im[:, q, p] = np.where(kept, -a_im, zero)
+        big_w[:, p, q] = big_w[:, q, p] = np.where(kept, w, zero)
+        return big_re, big_im, big_w
+
+    def _solve(self, vis, pairs, weights, flags, initial):
+        channels = vis.shape[0]
+        n = pairs.shape[0]
+        f32 = np.float32
+        half, zero, one = f32(0.5), f32(0), f32(1)
+        bsum = self._block_sum
+        with np.errstate(all="ignore"):
+            a_re, a_im, w = self._matrix(vis, pairs, weights, flags)
+            has = (w > 0).any(axis=2)
+            if initial is None:
+                g_re, g_im = np.ones((channels, n), f32), np.zeros((channels, n), f32)
+            else:
+                g_re, g_im = np.array(initial.real), np.array(initial.imag)  # (copies)
+            iterations = np.zeros(channels, np.int32)
+            converged = np.zeros(channels, bool)
+            for k in range(1, self.max_iterations + 1):
+                act = np.flatnonzero(~converged)
+                if not act.size:
+                    break
+                gr, gi = g_re[act], g_im[act]
+                s = gr * gr + gi * gi
+                gr_q, gi_q = gr[:, np.newaxis, :], gi[:, np.newaxis, :]
+                ar, ai = a_re[act], a_im[act]
+                num_re = bsum(ar * gr_q - ai * gi_q)
+                num_im = bsum(ar * gi_q + ai * gr_q)
+                den = bsum(w[act] * s[:, np.newaxis, :])
+                pos = den > 0
+                safe = np.where(pos, den, one)  # (no 0 / 0 where the quotient is not used)
+                new_re = np.where(pos, num_re / safe, gr)
+                new_im = np.where(pos, num_im / safe, gi)
+                if k % 2:
+                    g_re[act], g_im[act] = new_re, new_im
+                else:
+                    new_re = (new_re + gr) * half
+                    new_im = (new_im + gi) * half
+                    dr, di = new_re - gr, new_im - gi
+                    d = bsum(np.where(has[act], dr * dr + di * di, zero))
+                    norm = bsum(np.where(has[act], new_re * new_re + new_im * new_im, zero))
+                    g_re[act], g_im[act] = new_re, new_im
+                    converged[act] = d <= self.tol2 * norm
+                iterations[act] = k
+            status = np.where(converged, 0, self.NOT_CONVERGED).astype(np.uint8)
+            status[~has.any(axis=1)] |= np.uint8(self.NO_DATA)
+            # referencing
+            referenced = np.zeros(channels, bool)
+            if self.reference >= 0:
+                r_re, r_im = g_re[:, self.reference], g_im[:, self.reference]
+                m = np.sqrt(r_re * r_re + r_im * r_im)
+                referenced = has[:, self.reference] & (m > 0) & np.isfinite(m)
+                safe = np.where(referenced, m, one)
+                u_re, u_im = (r_re / safe)[:, np.newaxis], (-r_im / safe)[:, np.newaxis]
+                rows = referenced[:, np.newaxis]
+                turned_re = np.where(rows, g_re * u_re - g_im * u_im, g_re)
+                turned_im = np.where(rows, g_re * u_im + g_im * u_re, g_im)
+                g_re, g_im = turned_re, turned_im
+                g_im[:, self.reference] = np.where(referenced, zero, g_im[:, self.reference])
+            status[~referenced] |= np.uint8(self.NOT_REFERENCED)
+            if self.corrections:
+                s = g_re * g_re + g_im * g_im
+                pos = s > 0
+                safe = np.where(pos, s, one)
+                g_re = np.where(pos, g_re / safe, f32(np.nan))
+                g_im = np.where(pos, -g_im / safe, f32(np.nan))
+            gains = np.empty((channels, n), np.complex64)
+            gains.real[...] = np.where(has, g_re, f32(np.nan))
+            gains.imag[...] = np.where(has, g_im, f32(np.nan))
+            assert g_re.dtype == f32 and g_im.dtype == f32
+        return gains, iterations, status
+
+
 def check_ranges(ranges, baselines: Optional[int] = None) -> Tuple[Tuple[int, int], ...]:
     """`ranges` as a tuple of 1 to :attr:`RangePercentilesHost.MAX_RANGES` pairs of ints
     ``(start, stop)`` with ``0 <= start <= stop``, ``stop - start`` at most
