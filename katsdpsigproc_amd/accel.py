@@ -279,6 +279,14 @@ class DeviceArray:
 
         Supports ints, slices with positive step and ``np.newaxis``; missing trailing
         axes are taken whole (reference accel.py:588-654).
+
+        A slice selects what NumPy selects, ``len(range(start, stop, step))`` elements.
+        This departs from the reference, which counts ``(stop - start) // step`` and so
+        drops the last element whenever the step does not divide the extent (``[0:10:3]``
+        gives 3 elements there, 4 in NumPy): its own tests define a region copy as
+        ``expected[dest_region] = src[src_region]`` in NumPy, so NumPy's count is the
+        contract and the floor count a defect. A selection is empty only where NumPy
+        finds it empty.
         """
         if not isinstance(region, tuple):
             region = (region,)
@@ -299,8 +307,8 @@ class DeviceArray:
                 start, stop, step = item.indices(shape[axis])
                 if step <= 0:
                     raise IndexError("Only positive strides are supported")
-                count = (stop - start) // step
-                if count <= 0:
+                count = len(range(start, stop, step))
+                if count == 0:
                     raise IndexError("Empty slice selection")
                 origin += start * strides[axis]
                 out_shape.append(count)
