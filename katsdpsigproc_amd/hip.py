@@ -478,6 +478,8 @@ class CommandQueue(AbstractCommandQueue):
             elif isinstance(arg, np.generic):
                 if arg.dtype == np.complex64:
                     values.append((ctypes.c_float * 2)(arg.real, arg.imag))
+                elif arg.dtype == np.complex128:
+                    values.append((ctypes.c_double * 2)(arg.real, arg.imag))
                 elif arg.dtype in self._CTYPES:
                     values.append(self._CTYPES[arg.dtype](arg.item()))
                 else:

@@ -129,9 +129,14 @@ class HReduce(accel.Operation):
         wgsx, wgsy = self.template.wgsx, self.template.wgsy
         first, last = self.column_range
         scalars = [np.int32(first), np.int32(last - first), np.int32(src.padded_shape[1])]
+        # one workgroup per wgsy rows, side by side on dimension x: a launch is refused when
+        # dimension y has more than 65535 workgroups, x takes as many as 32 bits of threads
+        groups = accel.divup(src.shape[0], wgsy)
+        if wgsx * groups >= 1 << 32:
+            raise ValueError("too many rows for one launch of the hreduce kernel")
         self.command_queue.enqueue_kernel(
             self.kernel, [src.buffer, dest.buffer] + scalars,
-            global_size=(wgsx, accel.roundup(src.shape[0], wgsy)), local_size=(wgsx, wgsy))  # fmt: skip
+            global_size=(wgsx * groups, wgsy), local_size=(wgsx, wgsy))  # fmt: skip
 
     def parameters(self) -> Mapping[str, Any]:
         template = self.template

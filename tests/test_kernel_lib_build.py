@@ -1,5 +1,6 @@
 """The helper headers for run-time compiled kernels (kernels/wg_reduce.h,
-transpose_base.h, rank.h), without a GPU: every test kernel of tests/kernels/ is rendered
+transpose_base.h, rank.h) and the package's own kernel templates (fill, hreduce), without a
+GPU: every test kernel of tests/kernels/ and every template of accel.KERNEL_DIR is rendered
 and compiled for gfx950 by hipcc, device side only, and the headers are checked to
 include nothing that hiprtc would not find."""
 
@@ -38,11 +39,39 @@ RENDERINGS = [
     ("transpose_test.hip.in", {"ctype": "double2", "block": 32, "vtx": 2, "vty": 2}),
 ]  # fmt: skip
 
+# The package's own templates (accel.KERNEL_DIR) and the argument-passing test kernel. hreduce:
+# every element type the operation is tested with, with an operator that suits it, at one row
+# lane, at a partly filled last wavefront, at one wavefront per row and across wavefronts.
+_HREDUCE_OPS = {
+    "unsigned char": ("a | b", "0"), "short": ("min(a, b)", "32767"), "int": ("a + b", "0"),
+    "long long": ("a + b", "0"), "unsigned long long": ("max(a, b)", "0"),
+    "float": ("pick(a, b)", "INFINITY"), "double": ("a + b", "0.0"),
+}  # fmt: skip
+_PICK = "DEVICE_FN static inline float pick(float a, float b) { return fminf(a, b); }"
+RENDERINGS += [
+    ("hreduce.hip.in", {"type": ctype, "wgsx": wgsx, "wgsy": wgsy, "op": op, "identity": identity,
+                        "extra_code": _PICK if ctype == "float" else ""})
+    for wgsx, wgsy in [(1, 3), (16, 5), (64, 4), (512, 2)]
+    for ctype, (op, identity) in _HREDUCE_OPS.items()
+]  # fmt: skip
+RENDERINGS += [
+    ("fill.hip.in", {"ctype": ctype, "wgs": wgs})
+    for ctype, wgs in [("unsigned char", 1024), ("short", 64), ("int", 96), ("long long", 64),
+                       ("unsigned long long", 1), ("float", 256), ("double", 64), ("float2", 64),
+                       ("double2", 128)]
+]  # fmt: skip
+RENDERINGS.append(("args_test.hip.in", {}))
+
+
+def _rendering_id(name, keys):
+    if name == "hreduce.hip.in":  # type and geometry tell these apart
+        keys = {k: keys[k] for k in ("type", "wgsx", "wgsy")}
+    return "-".join([name.split("_")[0].split(".")[0]] + [str(v).replace(" ", "") for v in keys.values()])
+
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc is not installed")
 @pytest.mark.parametrize("name, keys", RENDERINGS,
-                         ids=["-".join([n.split("_")[0]] + [str(v).replace(" ", "") for v in k.values()])
-                              for n, k in RENDERINGS])  # fmt: skip
+                         ids=[_rendering_id(n, k) for n, k in RENDERINGS])
 def test_kernels_compile_for_gfx950(name, keys, tmp_path):
     keys = dict(keys, simd_group_size=64)
     text = accel.render_template(name, keys, extra_dirs=[KERNELS])
