@@ -611,6 +611,51 @@ int ksp_solve_gains(int device, void *stream, const void *vis, const float *weig
                     int pairs_stride, int initial_stride, int gains_stride, int max_iterations,
                     float tol2, int reference, int mask, int corrections);
 
+/* predict: model visibilities of up to 64 point sources and, optionally, the data divided by
+ * them, in one launch: the step in front of ksp_solve_gains for a calibrator that is not a unit
+ * source at the phase centre (no reference counterpart; bit for bit what rfi/host.py
+ * PredictHost computes; every step is one operation, rounded once, a multiply then an add,
+ * never an fma: float64 for the model, float32 for the division).
+ * freqs: float64 [channels], Hz; delays: float64 [n_sources][delays_stride], seconds, of which
+ * baselines per row are data; flux: float32 [channels][flux_stride], of which n_sources per row
+ * are data; model, vis, out_vis: complex64 [channels][stride]; weights, out_weights: float32;
+ * flags, out_flags: uint8. Baselines contiguous, one stride per array, in elements. Per
+ * channel c, baseline j and source s, in float64:
+ *   x = freqs[c] delays[s][j];  r = x - rint(x);  q = rint(4 r);  y = r - q 0.25;
+ *   z = y 6.283185307179586;  z2 = z z;
+ *   sn = (((((S5 z2 + S4) z2 + S3) z2 + S2) z2 + S1) z2 + S0) z;
+ *   cs = (((((C6 z2 + C5) z2 + C4) z2 + C3) z2 + C2) z2 + C1) z2 + C0;
+ *     S0..S5 = 1.0, -0.16666666666666666, 0.008333333333333333, -0.0001984126984126984,
+ *              2.7557319223985893e-06, -2.505210838544172e-08;
+ *     C0..C6 = 1.0, -0.5, 0.041666666666666664, -0.001388888888888889, 2.48015873015873e-05,
+ *              -2.755731922398589e-07, 2.08767569878681e-09;
+ *   (co, si) = (cs, sn), (-sn, cs), (-cs, -sn), (sn, -cs) for q = 0, 1, +-2, -1;
+ *   re += flux[c][s] co;  im -= flux[c][s] si     (from +0, s ascending);
+ * model[c][j] = M = (float32(re), float32(im)), to nearest. With vis, in float32:
+ *   d = M.re M.re + M.im M.im;  ok = 0 < d < inf;
+ *   out_vis[c][j] = ok ? ((v.re M.re + v.im M.im) / d, (v.im M.re - v.re M.im) / d) : v;
+ *   out_weights[c][j] = ok ? weights[c][j] d : 0;
+ *   out_flags[c][j] = flags[c][j] | (ok ? 0 : flag_value).
+ * NaN and infinities go through as IEEE gives them: a non-finite x gives a NaN model, and a
+ * sample whose model is zero, NaN, or has a d that underflows or overflows keeps its vis bit
+ * for bit, gets weight 0 and flag_value. model may be NULL if vis is given, and vis if model
+ * is; out_vis is given exactly when vis is; weights and out_weights are both NULL or both
+ * given, and only with vis; so are flags and out_flags. An output may be its input (the same
+ * pointer with the same stride: in place); otherwise it must share no byte with it. model
+ * must share no byte with any other array. n_sources is 1..64, flag_value 1..255, channels and
+ * baselines at least 1. Elements between baselines (or n_sources) and a stride are neither
+ * read nor written. 16-byte accesses need every sample array given (model included), and
+ * every row start of it, to be a multiple of 16 bytes; anything else takes a slower
+ * element-wise path with the same result. One kernel launch, no workspace, no atomics. Every
+ * argument is checked before any device call. */
+int ksp_predict(int device, void *stream, const double *freqs, const double *delays,
+                const float *flux, void *model, const void *vis, const float *weights,
+                const uint8_t *flags, void *out_vis, float *out_weights, uint8_t *out_flags,
+                int channels, int baselines, int n_sources, int delays_stride, int flux_stride,
+                int model_stride, int vis_stride, int weights_stride, int flags_stride,
+                int out_vis_stride, int out_weights_stride, int out_flags_stride,
+                int flag_value);
+
 /* range_percentiles: per channel and per range of baselines, the [0, 100, 25, 75, 50] %
  * amplitudes ("lower" element) of the samples that are neither NaN nor flagged under a mask,
  * how many those are, and the OR of the range's flags, all ranges in one launch (no reference

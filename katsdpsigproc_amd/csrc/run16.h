@@ -15,9 +15,9 @@
 // with and dropped. `wide` is an ordinary bool: where it is a constant at the call site, the
 // other path folds away.
 //
-// compress_weights.hip, flag_count.hip, apply_gains.hip and the row pass of sir.hip are written
-// on these helpers. average.hip and prepare.hip have the same layout but hold several arrays of a run
-// at once, and keep their own two paths (profiles/run16.md).
+// compress_weights.hip, flag_count.hip, apply_gains.hip, predict.hip and the row pass of sir.hip
+// are written on these helpers. average.hip and prepare.hip have the same layout but hold several
+// arrays of a run at once, and keep their own two paths (profiles/run16.md).
 #pragma once
 
 #define KSP_RUN 16

@@ -985,6 +985,179 @@ class SolveGainsHost:
         return gains, iterations, status
 
 
+class PredictHost:
+    """Model visibilities of point sources and, optionally, the data divided by them: the step
+    in front of :class:`SolveGainsHost` for a calibrator that is not a unit source at the phase
+    centre. ``min sum w |V - g_p conj(g_q) M|^2`` is the unit-model problem on ``V / M`` with
+    weights ``w |M|^2``, so the solver takes ``out_vis`` and ``out_weights`` as they are. No
+    reference counterpart; this class is the definition that the device operation
+    (:class:`.ingest.PredictTemplate`) matches bit for bit.
+
+    ``M[c, j] = sum_s flux[c, s] exp(-2 pi i freqs[c] delays[s, j])``: the caller applies
+    spectral index and primary beam to `flux`, and fixes the sign convention through the sign
+    of `delays` (:meth:`delays` computes them from ``uvw`` and direction cosines). Per channel
+    ``c``, baseline ``j`` and source ``s``, every step one float64 operation, rounded once (a
+    multiply, then an add, never an fma)::
+
+        x  = freqs[c] * delays[s, j]                      turns
+        r  = x - rint(x)                                  rint: to nearest, ties to even
+        q  = rint(4 * r)                                  -2 .. 2
+        y  = r - q * 0.25
+        z  = y * TWO_PI                                   |z| <= pi/4
+        z2 = z * z
+        sn = (((((S5*z2 + S4)*z2 + S3)*z2 + S2)*z2 + S1)*z2 + S0) * z       S = SIN_COEFFICIENTS
+        cs = (((((C6*z2 + C5)*z2 + C4)*z2 + C3)*z2 + C2)*z2 + C1)*z2 + C0   C = COS_COEFFICIENTS
+        (co, si) = (cs, sn), (-sn, cs), (-cs, -sn), (sn, -cs)    for q = 0, 1, +-2, -1
+        re = re + float64(flux[c, s]) * co
+        im = im - float64(flux[c, s]) * si
+
+    from ``re = im = +0`` with ``s`` ascending; ``model[c, j] = (float32(re), float32(im))``,
+    rounded to nearest. A negation flips the sign, so a zero keeps the sign it gets. The
+    coefficients are ``(-1)^k / (2k+1)!`` and ``(-1)^k / (2k)!`` as float64; ``(co, si)`` is
+    within 7e-12 of the true values, four orders below the float32 rounding of the result.
+
+    With `vis`, every step one float32 operation on the rounded model ``M``::
+
+        d  = M.re*M.re + M.im*M.im
+        ok = d > 0 and d < inf                            (false for NaN, underflow, overflow)
+        out_vis     = ok ? ((v.re*M.re + v.im*M.im) / d, (v.im*M.re - v.re*M.im) / d) : v
+        out_weights = ok ? w * d : 0
+        out_flags   = flags | (ok ? 0 : flag_value)
+
+    What follows from it:
+
+    * NaN and infinities go through as IEEE gives them: a non-finite ``x`` gives a NaN model.
+    * A sample without a usable model (zero, NaN, or ``d`` under- or overflowing) keeps its
+      visibility bit for bit, gets weight 0, "no data" as :class:`SolveGainsHost` reads it, and
+      is flagged.
+
+    Parameters
+    ----------
+    flag_value
+        Bits set in ``out_flags`` of a sample without a usable model, 1..255
+        (:func:`check_flag_byte`)
+    """
+
+    MAX_SOURCES = 64
+    SPEED_OF_LIGHT = 299792458.0
+    TWO_PI = 6.283185307179586
+    #: S0 .. S5
+    SIN_COEFFICIENTS = (1.0, -0.16666666666666666, 0.008333333333333333,
+                        -0.0001984126984126984, 2.7557319223985893e-06,
+                        -2.505210838544172e-08)  # fmt: skip
+    #: C0 .. C6
+    COS_COEFFICIENTS = (1.0, -0.5, 0.041666666666666664, -0.001388888888888889,
+                        2.48015873015873e-05, -2.755731922398589e-07,
+                        2.08767569878681e-09)  # fmt: skip
+
+    def __init__(self, flag_value: int = 64) -> None:
+        self.flag_value = check_flag_byte("flag_value", flag_value)
+
+    @classmethod
+    def delays(cls, uvw, lm) -> np.ndarray:
+        """float64 (n_sources, baselines): ``(u l + v m + w (sqrt(1 - l^2 - m^2) - 1)) / c``
+        for `uvw` (baselines, 3) in metres and the direction cosines `lm` (n_sources, 2).
+        ``ValueError`` for a wrong shape or a source with ``l^2 + m^2 > 1``."""
+        uvw = np.asarray(uvw, np.float64)
+        lm = np.asarray(lm, np.float64)
+        if uvw.ndim != 2 or uvw.shape[1] != 3:
+            raise ValueError(f"uvw must have shape (baselines, 3), not {uvw.shape}")
+        if lm.ndim != 2 or lm.shape[1] != 2:
+            raise ValueError(f"lm must have shape (n_sources, 2), not {lm.shape}")
+        l, m = lm[:, 0, np.newaxis], lm[:, 1, np.newaxis]
+        n2 = 1.0 - l * l - m * m
+        if not (n2 >= 0).all():
+            raise ValueError("lm has a source with l^2 + m^2 > 1")
+        u, v, w = uvw[np.newaxis, :, 0], uvw[np.newaxis, :, 1], uvw[np.newaxis, :, 2]
+        return (u * l + v * m + w * (np.sqrt(n2) - 1.0)) / cls.SPEED_OF_LIGHT
+
+    @classmethod
+    def cos_sin(cls, x: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """``(co, si)`` of the class docstring for float64 turns `x`."""
+        assert x.dtype == np.float64
+        s, c = cls.SIN_COEFFICIENTS, cls.COS_COEFFICIENTS
+        with np.errstate(all="ignore"):
+            r = x - np.rint(x)
+            q = np.rint(4.0 * r)
+            y = r - q * 0.25
+            z = y * cls.TWO_PI
+            z2 = z * z
+            sn = s[5]
+            for k in (4, 3, 2, 1, 0):
+                sn = sn * z2 + s[k]
+            sn = sn * z
+            cs = c[6]
+            for k in (5, 4, 3, 2, 1, 0):
+                cs = cs * z2 + c[k]
+        odd, half = np.abs(q) == 1.0, np.abs(q) == 2.0
+        co = np.where(odd, sn, cs)
+        si = np.where(odd, cs, sn)
+        co = np.where((q == 1.0) | half, -co, co)
+        si = np.where((q == -1.0) | half, -si, si)
+        return co, si
+
+    def __call__(self, freqs: np.ndarray, delays: np.ndarray, flux: np.ndarray,
+                 vis: Optional[np.ndarray] = None, weights: Optional[np.ndarray] = None,
+                 flags: Optional[np.ndarray] = None):  # fmt: skip
+        """``(model, out_vis, out_weights, out_flags)``, the last three ``None`` without `vis`
+        (and each of the last two without its input), for float64 `freqs` (channels,), float64
+        `delays` (n_sources, baselines), float32 `flux` (channels, n_sources), optional
+        complex64 `vis`, float32 `weights` and uint8 `flags` (all channels, baselines; the last
+        two only with `vis`). ``ValueError``, naming the argument, for a wrong dtype, rank or
+        shape (channels and baselines at least 1, n_sources 1..64). No argument is modified."""
+        freqs = _check_array("freqs", freqs, np.float64, "(channels,)",
+                             lambda s: len(s) == 1 and s[0] >= 1)  # fmt: skip
+        channels = freqs.shape[0]
+        delays = _check_array("delays", delays, np.float64,
+                              "(n_sources, baselines), n_sources 1..64",
+                              lambda s: len(s) == 2 and 1 <= s[0] <= self.MAX_SOURCES
+                              and s[1] >= 1)  # fmt: skip
+        n_sources, baselines = delays.shape
+        flux = _check_array("flux", flux, np.float32, "(channels, n_sources)",
+                            lambda s: s == (channels, n_sources))  # fmt: skip
+        shape = (channels, baselines)
+        if vis is not None:
+            vis = _check_array("vis", vis, np.complex64, "(channels, baselines)",
+                               lambda s: s == shape)  # fmt: skip
+        for name, value in (("weights", weights), ("flags", flags)):
+            if value is not None and vis is None:
+                raise ValueError(f"{name} given without vis")
+        if weights is not None:
+            weights = _check_array("weights", weights, np.float32, "(channels, baselines)",
+                                   lambda s: s == shape)  # fmt: skip
+        if flags is not None:
+            flags = _check_array("flags", flags, np.uint8, "(channels, baselines)",
+                                 lambda s: s == shape)  # fmt: skip
+        re = np.zeros(shape, np.float64)
+        im = np.zeros(shape, np.float64)
+        with np.errstate(all="ignore"):
+            for s in range(n_sources):
+                co, si = self.cos_sin(freqs[:, np.newaxis] * delays[s][np.newaxis, :])
+                amplitude = flux[:, s, np.newaxis].astype(np.float64)
+                re = re + amplitude * co
+                im = im - amplitude * si
+            model = np.empty(shape, np.complex64)
+            model.real[...] = re.astype(np.float32)
+            model.imag[...] = im.astype(np.float32)
+            if vis is None:
+                return model, None, None, None
+            m_re, m_im = model.real, model.imag
+            d = m_re * m_re + m_im * m_im
+            ok = (d > 0) & (d < np.inf)
+            safe = np.where(ok, d, np.float32(1))  # (the divisor of a sample that stays: no 0 / 0)
+            out_vis = np.empty(shape, np.complex64)
+            out_vis.real[...] = np.where(ok, (vis.real * m_re + vis.imag * m_im) / safe, vis.real)
+            out_vis.imag[...] = np.where(ok, (vis.imag * m_re - vis.real * m_im) / safe, vis.imag)
+            assert d.dtype == np.float32 and safe.dtype == np.float32
+            out_weights = None
+            if weights is not None:
+                out_weights = np.where(ok, weights * d, np.float32(0))
+        out_flags = None
+        if flags is not None:
+            out_flags = flags | np.where(ok, np.uint8(0), np.uint8(self.flag_value))
+        return model, out_vis, out_weights, out_flags
+
+
 def check_ranges(ranges, baselines: Optional[int] = None) -> Tuple[Tuple[int, int], ...]:
     """`ranges` as a tuple of 1 to :attr:`RangePercentilesHost.MAX_RANGES` pairs of ints
     ``(start, stop)`` with ``0 <= start <= stop``, ``stop - start`` at most

@@ -18,8 +18,10 @@ between averaging and the consumers of calibrated data: per-input gain correctio
 ``vis``, ``weights`` and ``flags`` in one launch, in place or not, bit for bit what
 :class:`.host.ApplyGainsHost` defines. And what produces those gains: per channel, the
 per-input gains of a point source solved with StEFCal in one launch, one workgroup per channel,
-bit for bit what :class:`.host.SolveGainsHost` defines. The classes follow DESIGN.md, "Adding
-an operation".
+bit for bit what :class:`.host.SolveGainsHost` defines. And the step in front of that for a field
+that is not one source at the phase centre: the model visibilities of up to 64 point sources,
+with float64 phases, and optionally the data divided by them, in one launch, bit for bit what
+:class:`.host.PredictHost` defines. The classes follow DESIGN.md, "Adding an operation".
 """
 
 import ctypes
@@ -668,6 +670,172 @@ class SolveGainsHostFromDevice:
         out = _native_op.run_once(fn, self.command_queue, given,
                                   ["gains", "iterations", "status"])  # fmt: skip
         return out[0], out[1], out[2]
+
+
+class PredictTemplate(_native_op.NativeTemplate):
+    """The step in front of :class:`SolveGainsTemplate` for a calibrator that is not a unit
+    source at the phase centre: the model visibilities of up to 64 point sources evaluated per
+    sample and, with `divide`, the ``vis`` that :class:`.device.Finalise` leaves divided by
+    them, the ``weights`` scaled to match and the samples without a usable model flagged, in
+    one kernel launch; see :class:`host.PredictHost` for every step.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    model
+        ``True``: there is a `model` slot
+    divide
+        ``True``: there are a `vis` and an `out_vis` slot
+    weights
+        ``True``: with `divide`, there are a `weights` and an `out_weights` slot
+    flags
+        ``True``: with `divide`, there are a `flags` and an `out_flags` slot
+    flag_value
+        As for :class:`host.PredictHost` (same errors)
+    tuning
+        The kernel picks its launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+
+    ``ValueError`` if neither `model` nor `divide` is set.
+    """
+
+    host_class = host.PredictHost
+    KERNEL = "ksp_predict"
+
+    def __init__(self, context: AbstractContext, model: bool = True, divide: bool = False,
+                 weights: bool = True, flags: bool = True, flag_value: int = 64,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        self.model = bool(model)
+        self.divide = bool(divide)
+        if not (self.model or self.divide):
+            raise ValueError("one of model and divide must be set")
+        self.weights = self.divide and bool(weights)
+        self.flags = self.divide and bool(flags)
+        self.flag_value = host.PredictHost(flag_value).flag_value
+        self._setup(context, tuning)
+
+
+class Predict(_native_op.NativeOperation):
+    """Concrete :class:`PredictTemplate` (``ValueError`` if `channels` or `baselines` is below
+    1 or `n_sources` outside 1..64).
+
+    .. rubric:: Slots
+
+    **freqs** : channels, float64
+    **delays** : n_sources x baselines, float64
+    **flux** : channels x n_sources, float32
+    **model** : channels x baselines, complex64 (only with ``model``)
+    **vis**, **out_vis** : channels x baselines, complex64 (only with ``divide``)
+    **weights**, **out_weights** : channels x baselines, float32 (only with ``weights``)
+    **flags**, **out_flags** : channels x baselines, uint8 (only with ``flags``)
+
+    Every padded dimension is an object of its own, so ``vis``, ``weights`` and ``flags`` can
+    be compounded with :class:`.device.Finalise`'s outputs and the ``out_*`` slots with the
+    inputs of :class:`SolveGains`, each taking the other's padding, while :class:`ApplyGains`
+    keeps reading what :class:`.device.Finalise` left. Binding one buffer to ``vis`` and
+    ``out_vis`` (and likewise to the other two pairs) divides in place.
+    """
+
+    def __init__(self, template: PredictTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int, n_sources: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        if channels < 1 or baselines < 1:
+            raise ValueError("channels and baselines must be at least 1")
+        if not 1 <= n_sources <= host.PredictHost.MAX_SOURCES:
+            raise ValueError(f"n_sources must be 1..{host.PredictHost.MAX_SOURCES}")
+        self.n_sources = n_sources
+
+        def samples(dtype) -> accel.IOSlot:
+            return accel.IOSlot((channels, accel.Dimension(baselines)), dtype)
+
+        self.slots["freqs"] = accel.IOSlot((accel.Dimension(channels),), np.float64)
+        self.slots["delays"] = accel.IOSlot((n_sources, accel.Dimension(baselines)), np.float64)
+        self.slots["flux"] = accel.IOSlot((channels, accel.Dimension(n_sources)), np.float32)
+        if template.model:
+            self.slots["model"] = samples(np.complex64)
+        for name, present, dtype in (("vis", template.divide, np.complex64),
+                                     ("weights", template.weights, np.float32),
+                                     ("flags", template.flags, np.uint8)):  # fmt: skip
+            if present:
+                self.slots[name] = samples(dtype)
+                self.slots["out_" + name] = samples(dtype)
+
+    def _run(self) -> None:
+        template = self.template
+
+        def optional(name: str, present: bool) -> Optional[accel.DeviceArray]:
+            return self.buffer(name) if present else None
+
+        delays, flux = self.buffer("delays"), self.buffer("flux")
+        model = optional("model", template.model)
+        vis, out_vis = optional("vis", template.divide), optional("out_vis", template.divide)
+        weights = optional("weights", template.weights)
+        out_weights = optional("out_weights", template.weights)
+        flags, out_flags = optional("flags", template.flags), optional("out_flags", template.flags)
+        self._launch(
+            self.buffer("freqs").buffer,
+            delays.buffer,
+            flux.buffer,
+            _native_op.pointer(model),
+            _native_op.pointer(vis),
+            _native_op.pointer(weights),
+            _native_op.pointer(flags),
+            _native_op.pointer(out_vis),
+            _native_op.pointer(out_weights),
+            _native_op.pointer(out_flags),
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(self.n_sources),
+            np.int32(delays.padded_shape[1]),
+            np.int32(flux.padded_shape[1]),
+            _native_op.stride(model),
+            _native_op.stride(vis),
+            _native_op.stride(weights),
+            _native_op.stride(flags),
+            _native_op.stride(out_vis),
+            _native_op.stride(out_weights),
+            _native_op.stride(out_flags),
+            np.int32(template.flag_value),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        template = self.template
+        return self._parameters(model=template.model, divide=template.divide,
+                                weights=template.weights, flags=template.flags,
+                                flag_value=template.flag_value, n_sources=self.n_sources)  # fmt: skip
+
+
+PredictTemplate.operation_class = Predict
+
+
+class PredictHostFromDevice:
+    """Make a :class:`PredictTemplate` callable like :class:`host.PredictHost`: ``(freqs,
+    delays, flux, vis=None, weights=None, flags=None)`` in, ``(model or None, out_vis or None,
+    out_weights or None, out_flags or None)`` out; allocates on every call. ``TypeError``
+    unless `vis`, `weights` and `flags` are each given exactly when the template has them."""
+
+    def __init__(self, template: PredictTemplate, command_queue: AbstractCommandQueue) -> None:
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, freqs: np.ndarray, delays: np.ndarray, flux: np.ndarray,
+                 vis: Optional[np.ndarray] = None, weights: Optional[np.ndarray] = None,
+                 flags: Optional[np.ndarray] = None):  # fmt: skip
+        template = self.template
+        _native_op.check_optional(vis, template.divide, "vis")
+        _native_op.check_optional(weights, template.weights, "weights")
+        _native_op.check_optional(flags, template.flags, "flags")
+        n_sources, baselines = np.shape(delays)
+        fn = template.instantiate(self.command_queue, len(freqs), baselines, n_sources)
+        given = {"freqs": freqs, "delays": delays, "flux": flux, "vis": vis, "weights": weights,
+                 "flags": flags}  # fmt: skip
+        present = {"model": template.model, "out_vis": template.divide,
+                   "out_weights": template.weights, "out_flags": template.flags}  # fmt: skip
+        names = [name for name, there in present.items() if there]
+        out = dict(zip(names, _native_op.run_once(fn, self.command_queue, given, names)))
+        return tuple(out.get(name) for name in present)
 
 
 class RangePercentilesTemplate(_native_op.NativeTemplate):
