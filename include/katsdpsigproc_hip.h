@@ -656,6 +656,52 @@ int ksp_predict(int device, void *stream, const double *freqs, const double *del
                 int out_vis_stride, int out_weights_stride, int out_flags_stride,
                 int flag_value);
 
+/* fit_delays: per input, the delay and phase whose phasor best matches the gains that
+ * ksp_solve_gains leaves across the band, and that phasor for every channel of the band, which
+ * is what ksp_apply_gains applies, in one launch (no reference counterpart; bit for bit what
+ * rfi/host.py FitDelaysHost computes; every step is one operation, rounded once, a multiply
+ * then an add, never an fma: float32 for the transform, float64 for the refinement).
+ * gains, model: complex64 [channels][stride], of which n_inputs per row are data; status:
+ * uint8 [channels] or NULL; delays: float64 [n_inputs], seconds; phasors: complex64
+ * [n_inputs]; amplitudes: float32 [n_inputs]; fit_status: uint8 [n_inputs]. Per input p:
+ *   x[c] = gains[c][p] if both parts are finite and (status is NULL or
+ *   status[c] & status_mask == 0), else 0; x[c] = 0 for c = channels .. n_fft - 1; n_kept
+ *   counts the kept channels.
+ *   Coarse, float32: X = the in-place radix-2 decimation-in-time transform of x with
+ *   W = exp(-2 pi i / n_fft): bit reversal, then stages s = 1 .. log2 n_fft, half = 2^(s-1),
+ *   butterfly (j, j + half) with tw = (float32(co), float32(-si)), (co, si) the cos_sin of
+ *   ksp_predict at (j mod half) / 2^s turns:
+ *     bt = (b.re tw.re - b.im tw.im, b.re tw.im + b.im tw.re);  a' = a + bt;  b' = a - bt;
+ *   P[k] = re re + im im; k0 = the lowest k at which P takes its largest value that is not NaN.
+ *   No fit (bit 0 of fit_status) if n_kept < 2, every P is NaN or that value is not in (0, inf).
+ *   Refinement, float64, from nu = k0 / n_fft, `refine` times: per kept channel
+ *     (co, si) = cos_sin(c nu);  e = (x.re co + x.im si, x.im co - x.re si);
+ *     D0 = sum e;  D1 = sum c e;  D2 = sum (c c) e, each the halving tree over Cpad terms
+ *     (the next power of two at or above channels; other terms +0):
+ *     n = Cpad; while n > 1: n /= 2, t[i] = t[i] + t[i + n] for i < n;
+ *     num = D1.im D0.re - D1.re D0.im;
+ *     den = 6.283185307179586 ((D1.re D1.re + D1.im D1.im) - (D2.re D0.re + D2.im D0.im));
+ *     step = num / den;  if den < 0 and |step| <= 1 / n_fft then nu = nu - step, else bit 1 of
+ *     fit_status is set and the loop ends (a NaN fails both tests).
+ *   Results, from D0 at the final nu: m = sqrt(D0.re D0.re + D0.im D0.im); no fit unless m is
+ *   in (0, inf); phasors[p] = (float32(D0.re / m), float32(D0.im / m));
+ *   amplitudes[p] = float32(m / n_kept); delays[p] = (nu - rint(nu)) / channel_width; and
+ *   with ph the rounded phasor and (co, si) = cos_sin(c nu), for every c < channels,
+ *   model[c][p] = (float32(ph.re co - ph.im si), float32(ph.re si + ph.im co)), the imaginary
+ *   part negated if corrections is 1. An input without a fit has NaN in delays, phasors,
+ *   amplitudes and its column of model.
+ * status and model may be NULL. channels is 1..8192, n_inputs at least 1, n_fft a power of two
+ * in 4..16384 and at least twice the channels, refine 0..8, status_mask 0..255, corrections 0
+ * or 1, channel_width finite and not 0. model must share no byte with gains. Elements between
+ * n_inputs and a stride are neither read nor written. One kernel launch, one workgroup per
+ * input with 8 n_fft bytes of LDS, no workspace, no atomics. Every argument is checked before
+ * any device call. */
+int ksp_fit_delays(int device, void *stream, const void *gains, const uint8_t *status,
+                   double *delays, void *phasors, float *amplitudes, uint8_t *fit_status,
+                   void *model, int channels, int n_inputs, int gains_stride, int model_stride,
+                   int n_fft, int refine, int status_mask, int corrections,
+                   double channel_width);
+
 /* range_percentiles: per channel and per range of baselines, the [0, 100, 25, 75, 50] %
  * amplitudes ("lower" element) of the samples that are neither NaN nor flagged under a mask,
  * how many those are, and the OR of the range's flags, all ranges in one launch (no reference

@@ -207,6 +207,10 @@ SIGNATURES = {
         c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
         c_int, c_int, c_int, c_int, c_int,
     ],
+    "ksp_fit_delays": [
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+        c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double,
+    ],
     "ksp_range_percentiles": [
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
         c_int, c_int, c_int, c_int, POINTER(c_int), c_int, c_int, c_int,

@@ -1158,6 +1158,264 @@ class PredictHost:
         return model, out_vis, out_weights, out_flags
 
 
+class FitDelaysHost:
+    """Per-input delay (K) fit to the gains that :class:`SolveGainsHost` solves: per input the
+    delay and phase whose phasor ``exp(i(phi + 2 pi c channel_width tau))`` best matches the
+    gains across the band, and that phasor for every channel of the band, kept or not, which is
+    what :class:`ApplyGainsHost` applies. No reference counterpart; this class is the
+    definition that the device operation (:class:`.ingest.FitDelaysTemplate`) matches bit for
+    bit.
+
+    *Kept channels.* ``x[c] = gains[c, p]`` if both parts are finite and `status` is absent or
+    ``status[c] & status_mask == 0``, else 0; channels ``channels .. n_fft-1`` are 0; ``n_kept``
+    counts the kept ones. The gains enter with their amplitudes, which is the maximum-likelihood
+    weighting for equal noise per channel: they are not normalised.
+
+    *Coarse search*, every step one float32 operation, rounded once (a multiply, then an add,
+    never an fma). ``X[k] = sum_c x[c] W^(c k)``, ``W = exp(-2 pi i / n_fft)``, is an in-place
+    radix-2 decimation-in-time transform: a bit-reversal permutation, then the stages
+    ``s = 1 .. log2 n_fft`` with ``half = 2^(s-1)``, where the butterfly on ``(j, j + half)``
+    has the twiddle ``tw = (float32(co), float32(-si))``, ``(co, si) =``
+    :meth:`PredictHost.cos_sin` ``((j mod half) / 2^s)``, and::
+
+        bt = (b.re*tw.re - b.im*tw.im, b.re*tw.im + b.im*tw.re);  a' = a + bt;  b' = a - bt
+
+    ``P[k] = re*re + im*im`` and ``k0`` is the lowest ``k`` at which ``P`` takes its largest
+    value that is not NaN. There is *no fit* (bit 0 of ``fit_status``) if ``n_kept < 2``, every
+    ``P`` is NaN, or that largest value is not in ``(0, inf)``.
+
+    *Refinement*, every step one float64 operation, from ``nu = k0 / n_fft`` turns per channel,
+    `refine` times. For each kept channel ``(co, si) = cos_sin(float64(c) * nu)``,
+    ``e = (x.re*co + x.im*si, x.im*co - x.re*si)``, and ``D0 = sum e``, ``D1 = sum c*e``,
+    ``D2 = sum (c*c)*e``, where every sum is the halving tree over ``Cpad`` terms (the next
+    power of two at or above ``channels``; the terms of the other channels are +0):
+    ``n = Cpad; while n > 1: n //= 2; t[:n] = t[:n] + t[n:2n]``. Then::
+
+        num  = D1.im*D0.re - D1.re*D0.im
+        den  = TWO_PI * ((D1.re*D1.re + D1.im*D1.im) - (D2.re*D0.re + D2.im*D0.im))
+        step = num / den
+        den < 0 and |step| <= 1/n_fft ?  nu = nu - step  :  set bit 1 and stop
+
+    which is Newton's method on ``|sum x[c] exp(-2 pi i c nu)|^2``, the likelihood of a single
+    tone. A NaN fails both tests.
+
+    *Results*, from ``D0`` at the final ``nu``: ``m = sqrt(D0.re*D0.re + D0.im*D0.im)``; no fit
+    unless ``m`` is in ``(0, inf)``; ``phasors[p] = (float32(D0.re/m), float32(D0.im/m))``, the
+    phase at channel 0; ``amplitudes[p] = float32(m / n_kept)``;
+    ``delays[p] = (nu - rint(nu)) / channel_width``; and with ``ph`` the rounded phasor as
+    float64 and ``(co, si) = cos_sin(float64(c) * nu)``, ``model[c, p] = (float32(ph.re*co -
+    ph.im*si), float32(ph.re*si + ph.im*co))``, the imaginary part negated with `corrections`
+    (for a unit modulus the reciprocal). An input without a fit has NaN in ``delays``,
+    ``phasors``, ``amplitudes`` and its column of ``model``.
+
+    Parameters
+    ----------
+    channel_width
+        Hz from one channel to the next, finite and not 0; negative for a band stored in
+        descending frequency
+    n_fft
+        Length of the zero-padded transform: a power of two in 4..16384, at least twice the
+        channels. ``None``: the smallest power of two at or above four times the channels, at
+        most 16384.
+    refine
+        Newton steps, 0..8
+    status_mask
+        Bits of `status` that exclude a channel, 0..255 (:func:`check_mask_byte`)
+    corrections
+        ``True``: ``model`` is the conjugate phasor
+    """
+
+    MIN_FFT = 4
+    MAX_FFT = 16384
+    MAX_CHANNELS = MAX_FFT // 2
+    MAX_REFINE = 8
+    NO_FIT, STEP_REJECTED = 1, 2
+    TWO_PI = PredictHost.TWO_PI
+
+    def __init__(self, channel_width: float, n_fft: Optional[int] = None, refine: int = 3,
+                 status_mask: int = 0xFF, corrections: bool = False) -> None:  # fmt: skip
+        try:
+            width = float(channel_width)
+        except (TypeError, ValueError):
+            raise ValueError(f"channel_width {channel_width!r} is not a number") from None
+        if not np.isfinite(width) or width == 0:
+            raise ValueError(f"channel_width {channel_width!r} must be finite and not 0")
+        self.channel_width = width
+        self.n_fft = None if n_fft is None else self.check_n_fft(n_fft)
+        if isinstance(refine, (bool, np.bool_)) or not isinstance(refine, (int, np.integer)):
+            raise TypeError(f"refine {refine!r} is not an integer")
+        if not 0 <= refine <= self.MAX_REFINE:
+            raise ValueError(f"refine must be 0..{self.MAX_REFINE}")
+        self.refine = int(refine)
+        self.status_mask = check_mask_byte("status_mask", status_mask)
+        self.corrections = bool(corrections)
+
+    @classmethod
+    def check_n_fft(cls, n_fft) -> int:
+        """`n_fft` as an int that is a power of two in 4..16384 (``ValueError`` otherwise,
+        ``TypeError`` for a value that is not an integer)."""
+        if isinstance(n_fft, (bool, np.bool_)) or not isinstance(n_fft, (int, np.integer)):
+            raise TypeError(f"n_fft {n_fft!r} is not an integer")
+        if not cls.MIN_FFT <= n_fft <= cls.MAX_FFT or n_fft & (n_fft - 1):
+            raise ValueError(f"n_fft must be a power of two in {cls.MIN_FFT}..{cls.MAX_FFT}")
+        return int(n_fft)
+
+    def transform_length(self, channels: int, n_inputs: int = 1) -> int:
+        """The length of the transform for a band of `channels`: `n_fft`, or its default.
+        ``ValueError`` if `channels` is outside 1..8192, `n_inputs` below 1 or `n_fft` below
+        twice the channels."""
+        if not 1 <= channels <= self.MAX_CHANNELS:
+            raise ValueError(f"channels must be 1..{self.MAX_CHANNELS}")
+        if n_inputs < 1:
+            raise ValueError("n_inputs must be at least 1")
+        if self.n_fft is None:
+            n_fft = self.MIN_FFT
+            while n_fft < 4 * channels and n_fft < self.MAX_FFT:
+                n_fft *= 2
+            return n_fft
+        if self.n_fft < 2 * channels:
+            raise ValueError(f"n_fft {self.n_fft} is below twice the channels, {2 * channels}")
+        return self.n_fft
+
+    @staticmethod
+    def _tree_sum(terms: np.ndarray) -> np.ndarray:
+        """The halving tree over the first axis, whose length is a power of two."""
+        n = terms.shape[0]
+        while n > 1:
+            n //= 2
+            terms = terms[:n] + terms[n : 2 * n]
+        return terms[0]
+
+    @classmethod
+    def transform(cls, x_re: np.ndarray, x_im: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """The transform of the class docstring along the first axis of the float32 arrays
+        `x_re` and `x_im` (n_fft, ...), as two new arrays."""
+        n_fft = x_re.shape[0]
+        bits = n_fft.bit_length() - 1
+        assert x_re.dtype == np.float32 and x_im.dtype == np.float32 and n_fft == 1 << bits
+        index = np.arange(n_fft)
+        reverse = np.zeros(n_fft, np.int64)
+        for bit in range(bits):
+            reverse |= ((index >> bit) & 1) << (bits - 1 - bit)
+        rest = x_re.shape[1:]
+        re, im = x_re[reverse], x_im[reverse]
+        with np.errstate(all="ignore"):
+            for s in range(1, bits + 1):
+                half = 1 << (s - 1)
+                co, si = PredictHost.cos_sin(np.arange(half, dtype=np.float64) / (1 << s))
+                shape = (half,) + (1,) * len(rest)
+                tw_re = co.astype(np.float32).reshape(shape)
+                tw_im = (-si).astype(np.float32).reshape(shape)
+                re = re.reshape((-1, 2, half) + rest)
+                im = im.reshape((-1, 2, half) + rest)
+                a_re, a_im, b_re, b_im = re[:, 0], im[:, 0], re[:, 1], im[:, 1]
+                bt_re = b_re * tw_re - b_im * tw_im
+                bt_im = b_re * tw_im + b_im * tw_re
+                re = np.stack([a_re + bt_re, a_re - bt_re], axis=1)
+                im = np.stack([a_im + bt_im, a_im - bt_im], axis=1)
+        assert re.dtype == np.float32 and im.dtype == np.float32
+        return re.reshape((n_fft,) + rest), im.reshape((n_fft,) + rest)
+
+    def _kept(self, gains: np.ndarray, status: Optional[np.ndarray]) -> np.ndarray:
+        kept = np.isfinite(gains.real) & np.isfinite(gains.imag)
+        if status is not None:
+            kept &= ((status & np.uint8(self.status_mask)) == 0)[:, np.newaxis]
+        return kept
+
+    def _sums(self, x_re, x_im, kept, nu):
+        """``D0, D1, D2`` as six float64 (n_inputs,) arrays for float64 `x_re`, `x_im`
+        (Cpad, n_inputs), zero where not `kept`, at `nu` (n_inputs,)."""
+        c = np.arange(x_re.shape[0], dtype=np.float64)[:, np.newaxis]
+        co, si = PredictHost.cos_sin(c * nu[np.newaxis, :])
+        zero = np.float64(0)
+        e_re = np.where(kept, x_re * co + x_im * si, zero)
+        e_im = np.where(kept, x_im * co - x_re * si, zero)
+        c2 = c * c
+        tree = self._tree_sum
+        return (tree(e_re), tree(e_im), tree(np.where(kept, c * e_re, zero)),
+                tree(np.where(kept, c * e_im, zero)), tree(np.where(kept, c2 * e_re, zero)),
+                tree(np.where(kept, c2 * e_im, zero)))  # fmt: skip
+
+    def __call__(self, gains: np.ndarray, status: Optional[np.ndarray] = None):
+        """``(delays, phasors, amplitudes, fit_status, model)``: float64, complex64, float32
+        and uint8 (n_inputs,) and complex64 (channels, n_inputs), for complex64 `gains`
+        (channels, n_inputs) and optional uint8 `status` (channels,). ``ValueError``, naming
+        the argument, for a wrong dtype, rank or shape (channels 1..8192, n_inputs at least 1)
+        and for an `n_fft` below twice the channels. No argument is modified."""
+        gains = _check_array("gains", gains, np.complex64, "(channels, n_inputs)",
+                             lambda s: len(s) == 2 and 1 <= s[0] <= self.MAX_CHANNELS
+                             and s[1] >= 1)  # fmt: skip
+        channels, n_inputs = gains.shape
+        if status is not None:
+            status = _check_array("status", status, np.uint8, "(channels,)",
+                                  lambda s: s == (channels,))  # fmt: skip
+        n_fft = self.transform_length(channels, n_inputs)
+        f32, f64 = np.float32, np.float64
+        kept = self._kept(gains, status)
+        n_kept = kept.sum(axis=0)
+        x_re = np.zeros((n_fft, n_inputs), f32)
+        x_im = np.zeros((n_fft, n_inputs), f32)
+        x_re[:channels] = np.where(kept, gains.real, f32(0))
+        x_im[:channels] = np.where(kept, gains.imag, f32(0))
+        with np.errstate(all="ignore"):
+            t_re, t_im = self.transform(x_re, x_im)
+            power = t_re * t_re + t_im * t_im
+            assert power.dtype == f32
+            ranked = np.where(np.isnan(power), f32(-1), power)  # (no power is negative)
+            k0 = np.argmax(ranked, axis=0)  # the first of equal values
+            peak = ranked[k0, np.arange(n_inputs)]
+            no_fit = (n_kept < 2) | ~((peak > 0) & (peak < np.inf))
+            fit_status = np.zeros(n_inputs, np.uint8)
+
+            c_pad = 1
+            while c_pad < channels:
+                c_pad *= 2
+            wide_re = np.zeros((c_pad, n_inputs), f64)
+            wide_im = np.zeros((c_pad, n_inputs), f64)
+            wide_re[:channels] = x_re[:channels]
+            wide_im[:channels] = x_im[:channels]
+            wide_kept = np.zeros((c_pad, n_inputs), bool)
+            wide_kept[:channels] = kept
+            nu = k0.astype(f64) / f64(n_fft)
+            active = ~no_fit
+            for _ in range(self.refine):
+                if not active.any():
+                    break
+                d0r, d0i, d1r, d1i, d2r, d2i = self._sums(wide_re, wide_im, wide_kept, nu)
+                num = d1i * d0r - d1r * d0i
+                den = self.TWO_PI * ((d1r * d1r + d1i * d1i) - (d2r * d0r + d2i * d0i))
+                step = num / den
+                accept = (den < 0) & (np.abs(step) <= 1.0 / n_fft)
+                nu = np.where(active & accept, nu - step, nu)
+                fit_status[active & ~accept] |= np.uint8(self.STEP_REJECTED)
+                active = active & accept
+            d0r, d0i = self._sums(wide_re, wide_im, wide_kept, nu)[:2]
+            m = np.sqrt(d0r * d0r + d0i * d0i)
+            no_fit |= ~((m > 0) & (m < np.inf))
+            fit_status[no_fit] |= np.uint8(self.NO_FIT)
+            safe = np.where(no_fit, f64(1), m)  # (no 0 / 0 where the quotient is not used)
+            ph_re = np.where(no_fit, f32(np.nan), (d0r / safe).astype(f32))
+            ph_im = np.where(no_fit, f32(np.nan), (d0i / safe).astype(f32))
+            amplitudes = np.where(no_fit, f32(np.nan),
+                                  (m / np.maximum(n_kept, 1).astype(f64)).astype(f32))  # fmt: skip
+            delays = np.where(no_fit, np.nan, (nu - np.rint(nu)) / self.channel_width)
+            c = np.arange(channels, dtype=f64)[:, np.newaxis]
+            co, si = PredictHost.cos_sin(c * nu[np.newaxis, :])
+            wide_ph_re, wide_ph_im = ph_re.astype(f64), ph_im.astype(f64)
+            model_re = (wide_ph_re * co - wide_ph_im * si).astype(f32)
+            model_im = (wide_ph_re * si + wide_ph_im * co).astype(f32)
+            if self.corrections:
+                model_im = -model_im
+        phasors = np.empty(n_inputs, np.complex64)
+        phasors.real[...] = ph_re
+        phasors.imag[...] = ph_im
+        model = np.empty((channels, n_inputs), np.complex64)
+        model.real[...] = np.where(no_fit, f32(np.nan), model_re)
+        model.imag[...] = np.where(no_fit, f32(np.nan), model_im)
+        assert amplitudes.dtype == f32 and delays.dtype == f64
+        return delays, phasors, amplitudes, fit_status, model
+
+
 def check_ranges(ranges, baselines: Optional[int] = None) -> Tuple[Tuple[int, int], ...]:
     """`ranges` as a tuple of 1 to :attr:`RangePercentilesHost.MAX_RANGES` pairs of ints
     ``(start, stop)`` with ``0 <= start <= stop``, ``stop - start`` at most

@@ -21,7 +21,10 @@ per-input gains of a point source solved with StEFCal in one launch, one workgro
 bit for bit what :class:`.host.SolveGainsHost` defines. And the step in front of that for a field
 that is not one source at the phase centre: the model visibilities of up to 64 point sources,
 with float64 phases, and optionally the data divided by them, in one launch, bit for bit what
-:class:`.host.PredictHost` defines. The classes follow DESIGN.md, "Adding an operation".
+:class:`.host.PredictHost` defines. And the step behind the solver: per input, the delay and
+phase fitted to the solved gains across the band and the smooth phasor that is applied in their
+place, in one launch with one workgroup per input, bit for bit what
+:class:`.host.FitDelaysHost` defines. The classes follow DESIGN.md, "Adding an operation".
 """
 
 import ctypes
@@ -836,6 +839,146 @@ class PredictHostFromDevice:
         names = [name for name, there in present.items() if there]
         out = dict(zip(names, _native_op.run_once(fn, self.command_queue, given, names)))
         return tuple(out.get(name) for name in present)
+
+
+class FitDelaysTemplate(_native_op.NativeTemplate):
+    """The first thing a pipeline does with the gains of :class:`SolveGainsTemplate`: per
+    input, the delay and phase whose phasor best matches them across the band, and that
+    smooth, unit-modulus phasor for every channel, the ones the solver lost included, which is
+    what :class:`ApplyGainsTemplate` applies; one kernel launch with one workgroup per input;
+    see :class:`host.FitDelaysHost` for every step.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    channel_width, n_fft, refine, status_mask, corrections
+        As for :class:`host.FitDelaysHost` (same errors)
+    status
+        ``True``: there is a `status` slot (:class:`SolveGains`'s)
+    model
+        ``True``: there is a `model` slot
+    tuning
+        The kernel picks its launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.FitDelaysHost
+    KERNEL = "ksp_fit_delays"
+
+    def __init__(self, context: AbstractContext, channel_width: float,
+                 n_fft: Optional[int] = None, refine: int = 3, status: bool = True,
+                 status_mask: int = 0xFF, model: bool = True, corrections: bool = False,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        self.checked = host.FitDelaysHost(channel_width, n_fft, refine, status_mask, corrections)
+        self.channel_width = self.checked.channel_width
+        self.n_fft = self.checked.n_fft
+        self.refine = self.checked.refine
+        self.status = bool(status)
+        self.status_mask = self.checked.status_mask
+        self.model = bool(model)
+        self.corrections = self.checked.corrections
+        self._setup(context, tuning)
+
+
+class FitDelays(_native_op.NativeOperation):
+    """Concrete :class:`FitDelaysTemplate` (``ValueError`` if `channels` is outside 1..8192,
+    `n_inputs` below 1 or the template's `n_fft` below twice the channels).
+
+    .. rubric:: Slots
+
+    **gains** : channels x n_inputs, complex64
+    **status** : channels, uint8 (only with ``status``)
+    **delays** : n_inputs, float64
+    **phasors** : n_inputs, complex64
+    **amplitudes** : n_inputs, float32
+    **fit_status** : n_inputs, uint8
+    **model** : channels x n_inputs, complex64 (only with ``model``)
+
+    Every padded dimension is an object of its own, so ``gains`` and ``status`` can be
+    compounded with :class:`SolveGains`'s outputs and ``model`` with :class:`ApplyGains`'s
+    ``gains``, each taking the other's padding.
+    """
+
+    def __init__(self, template: FitDelaysTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, n_inputs: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, n_inputs, allocator)
+        self.n_inputs = n_inputs
+        self.n_fft = template.checked.transform_length(channels, n_inputs)
+
+        def per_input(dtype) -> accel.IOSlot:
+            return accel.IOSlot((accel.Dimension(n_inputs),), dtype)
+
+        def per_channel() -> accel.IOSlot:
+            return accel.IOSlot((channels, accel.Dimension(n_inputs)), np.complex64)
+
+        self.slots["gains"] = per_channel()
+        if template.status:
+            self.slots["status"] = accel.IOSlot((accel.Dimension(channels),), np.uint8)
+        self.slots["delays"] = per_input(np.float64)
+        self.slots["phasors"] = per_input(np.complex64)
+        self.slots["amplitudes"] = per_input(np.float32)
+        self.slots["fit_status"] = per_input(np.uint8)
+        if template.model:
+            self.slots["model"] = per_channel()
+
+    def _run(self) -> None:
+        template = self.template
+        gains = self.buffer("gains")
+        status = self.buffer("status") if template.status else None
+        model = self.buffer("model") if template.model else None
+        self._launch(
+            gains.buffer,
+            _native_op.pointer(status),
+            self.buffer("delays").buffer,
+            self.buffer("phasors").buffer,
+            self.buffer("amplitudes").buffer,
+            self.buffer("fit_status").buffer,
+            _native_op.pointer(model),
+            np.int32(self.channels),
+            np.int32(self.n_inputs),
+            np.int32(gains.padded_shape[1]),
+            _native_op.stride(model),
+            np.int32(self.n_fft),
+            np.int32(template.refine),
+            np.int32(template.status_mask),
+            np.int32(template.corrections),
+            np.float64(template.channel_width),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        template = self.template
+        return {"channel_width": template.channel_width, "n_fft": self.n_fft,
+                "refine": template.refine, "status": template.status,
+                "status_mask": template.status_mask, "model": template.model,
+                "corrections": template.corrections, "channels": self.channels,
+                "n_inputs": self.n_inputs}  # fmt: skip
+
+
+FitDelaysTemplate.operation_class = FitDelays
+
+
+class FitDelaysHostFromDevice:
+    """Make a :class:`FitDelaysTemplate` callable like :class:`host.FitDelaysHost`: ``(gains,
+    status=None)`` in, ``(delays, phasors, amplitudes, fit_status, model or None)`` out;
+    allocates on every call. ``TypeError`` unless `status` is given exactly when the template
+    has it."""
+
+    def __init__(self, template: FitDelaysTemplate, command_queue: AbstractCommandQueue) -> None:
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, gains: np.ndarray, status: Optional[np.ndarray] = None):
+        template = self.template
+        _native_op.check_optional(status, template.status, "status")
+        channels, n_inputs = np.shape(gains)
+        fn = template.instantiate(self.command_queue, channels, n_inputs)
+        names = ["delays", "phasors", "amplitudes", "fit_status"] + (
+            ["model"] if template.model else [])  # fmt: skip
+        out = _native_op.run_once(fn, self.command_queue, {"gains": gains, "status": status},
+                                  names)  # fmt: skip
+        return tuple(out) + (() if template.model else (None,))
 
 
 class RangePercentilesTemplate(_native_op.NativeTemplate):
