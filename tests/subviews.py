@@ -19,6 +19,7 @@ The layout functions work on NumPy arrays alone (tests/test_subviews.py tests th
 GPU); :class:`DeviceView` and :func:`flat_device_array` / :func:`read_flat` put them on a device.
 """
 
+import contextlib
 import ctypes
 
 import numpy as np
@@ -137,6 +138,39 @@ class DeviceView:
                 f"{self.layout.locate(int(np.flatnonzero(~same)[0]))}"  # fmt: skip
             return np.ascontiguousarray(self.layout.view(flat))
         return check_host(flat, self.layout, name)
+
+
+class CompactViews:
+    """The view factory of the raw-ABI tests: ``views(role, dtype, data, stride, offset,
+    poison)`` gives (view, pointer to the first element of data), `role` being the name of the
+    launcher's argument. Here every view is a :class:`DeviceView` with the stride asked for;
+    tests/farviews.py has a factory that moves chosen roles far apart, so the bodies take the
+    strides they hand to a launcher from ``view.stride``."""
+
+    def __init__(self, context, queue):
+        self.context, self.queue = context, queue
+
+    def __call__(self, role, dtype, data, stride, offset=0, poison=False):
+        return flat_device_array(self.context, self.queue, dtype, data, stride, offset, poison)
+
+    def shared_stride(self, like, arrays):
+        """The one stride of `arrays`, (role, rows, cols, dtype) each, that a launcher takes
+        for several arrays at once: `like`, the compact stride, here."""
+        return like
+
+    def mark(self):
+        """A point in time for :meth:`release`."""
+        return None
+
+    def release(self, mark):
+        """The views made since `mark` are done with (a factory with an arena reuses it)."""
+
+    @contextlib.contextmanager
+    def scope(self):
+        """Views made inside the block are done with at its end."""
+        mark = self.mark()
+        yield
+        self.release(mark)
 
 
 def flat_device_array(context, queue, dtype, data, stride, offset, poison=False):

@@ -17,7 +17,7 @@ import pytest
 
 from tests import inputs
 from tests import inputs_accumulate_block as data
-from tests.subviews import SENTINEL, flat_device_array, poison_array, sentinel_array
+from tests.subviews import SENTINEL, CompactViews, flat_device_array, poison_array, sentinel_array
 
 pytestmark = pytest.mark.gpu
 
@@ -218,34 +218,40 @@ def test_against_single_launches(mode, context, command_queue):
         data.assert_same(single.buffer(name).get(queue), g, f"{name}, block against launches")
 
 
-def check_raw_abi(context, queue, mode, n_dumps, baselines, offset, strides, odd_one_out=None):
+def check_raw_abi(context, queue, mode, n_dumps, baselines, offset, strides, odd_one_out=None,
+                  make_views=None):
     """The C function on sub-views `offset` elements into their allocations with the row
     stride `strides` gives each kind; `odd_one_out`, (dump, offset), moves the `vis` of that
-    dump alone. The accumulators start from what two other dumps leave."""
+    dump alone. The accumulators start from what two other dumps leave. `make_views` makes the
+    arrays (tests/subviews.py: CompactViews unless given); the strides the launcher gets are
+    those of the views it made."""
     from katsdpsigproc_amd import _lib
+
+    make_views = make_views or CompactViews(context, queue)
+    strides = dict(strides)
+
+    def make(name, dtype, value, at=offset, poison=False):
+        view = make_views(name, dtype, value, strides[name], at, poison)[0]
+        strides[name] = view.stride
+        return view
 
     channels = 6
     dumps = data.make_dumps(channels, baselines)
     selected = data.select(dumps[:n_dumps], True, mode)
     start = data.host_accumulate(data.select(dumps[6:8], True, mode, False), mode)
     dtypes = {"vis": np.complex64, "weights": np.float32, "flags": np.uint8}
-    acc = {name: flat_device_array(context, queue, dtypes[name[4:]], value, strides[name], offset)[0]
-           for name, value in zip(ACC, start)}  # fmt: skip
+    acc = {name: make(name, dtypes[name[4:]], value) for name, value in zip(ACC, start)}
     views = {"vis": [], "flags": [], "weights": [], "mask": []}
     for d, (vis, flags, weights, mask) in enumerate(selected):
         vis_offset = odd_one_out[1] if odd_one_out and odd_one_out[0] == d else offset
-        views["vis"].append(flat_device_array(
-            context, queue, np.complex64, vis, strides["vis"], vis_offset, poison=True)[0])
-        views["flags"].append(flat_device_array(
-            context, queue, np.uint8, flags, strides["flags"], offset, poison=True)[0])
-        views["weights"].append(flat_device_array(
-            context, queue, np.float32, weights, strides["weights"], offset, poison=True)[0])
+        views["vis"].append(make("vis", np.complex64, vis, vis_offset, poison=True))
+        views["flags"].append(make("flags", np.uint8, flags, poison=True))
+        views["weights"].append(make("weights", np.float32, weights, poison=True))
         if mode == "CHANNEL" and d == 0:
             views["mask"] = [flat_device_array(context, queue, np.uint8, mask[np.newaxis, :],
                                                channels, offset, poison=True)[0]] * n_dumps  # fmt: skip
         elif mode == "FULL":
-            views["mask"].append(flat_device_array(
-                context, queue, np.uint8, mask, strides["mask"], offset, poison=True)[0])
+            views["mask"].append(make("mask", np.uint8, mask, poison=True))
 
     def pointers(kind):
         return (ctypes.c_void_p * n_dumps)(*[view.address for view in views[kind]])

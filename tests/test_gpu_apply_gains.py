@@ -10,7 +10,7 @@ import pytest
 from tests import inputs
 from tests import inputs_apply_gains as gen
 from tests.inputs_apply_gains import assert_same
-from tests.subviews import flat_device_array, poison_array, sentinel_array
+from tests.subviews import CompactViews, poison_array, sentinel_array
 from tests.test_gpu_prepare import N_AUTO, chain_dump
 
 pytestmark = pytest.mark.gpu
@@ -222,11 +222,19 @@ def test_raw_abi_subviews(offset, strides, channels, baselines, n_inputs, contex
     elements and strides that keep the rows on 16 bytes take the 16-byte path from the middle
     of an allocation; 4 elements with such strides leave the flags off 16 bytes. The variants
     rotate; in place and out of place both."""
+    check_raw_abi(offset, strides, channels, baselines, n_inputs, context, command_queue)
+
+
+def check_raw_abi(offset, strides, channels, baselines, n_inputs, context, command_queue,
+                  views=None, variant=None):
+    """`views` makes the arrays (tests/subviews.py: CompactViews unless given) and may choose
+    other strides of the same kind; `variant` instead of the one that is due by rotation."""
     from katsdpsigproc_amd import _lib
 
     queue = command_queue
+    views = views or CompactViews(context, queue)
     seed = 31 * offset + baselines
-    weights, flags = VARIANTS[seed % 4]
+    weights, flags = variant or VARIANTS[seed % 4]
     case = gen.make_case(seed, channels, baselines, n_inputs, gen.PATTERNS[seed % 5])
     data_strides, gains_stride = strides(baselines, n_inputs)
     want = want_of(case, weights, flags)
@@ -235,11 +243,13 @@ def test_raw_abi_subviews(offset, strides, channels, baselines, n_inputs, contex
                          data_strides))  # fmt: skip
 
     def view(name, data, stride, poison):
-        return flat_device_array(context, queue, data.dtype, data, stride, offset, poison=poison)
+        return views(name, data.dtype, data, stride, offset, poison=poison)
 
     d_gains = view("gains", case["gains"], gains_stride, True)
     d_inputs = view("inputs", case["inputs"], 2, True)
+    mark = views.mark()
     for in_place in (False, True):
+        views.release(mark)  # (the arrays of the round before)
         d_in, d_out = {}, {}
         for kind in kinds:
             # in place the array is an output: sentinels around it instead of poison
@@ -260,7 +270,7 @@ def test_raw_abi_subviews(offset, strides, channels, baselines, n_inputs, contex
                   ptr(d_in, "vis"), ptr(d_in, "weights"), ptr(d_in, "flags"), d_gains[1],
                   d_inputs[1], ptr(d_out, "vis"), ptr(d_out, "weights"), ptr(d_out, "flags"),
                   channels, baselines, n_inputs, stride(d_in, "vis"), stride(d_in, "weights"),
-                  stride(d_in, "flags"), gains_stride, stride(d_out, "vis"),
+                  stride(d_in, "flags"), d_gains[0].stride, stride(d_out, "vis"),
                   stride(d_out, "weights"), stride(d_out, "flags"), 128)  # fmt: skip
         for kind, w in zip(("vis", "weights", "flags"), want):
             if kind in kinds:

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from tests import inputs
-from tests.subviews import SENTINEL, flat_device_array, read_flat, sentinel_array
+from tests.subviews import SENTINEL, CompactViews, flat_device_array, read_flat, sentinel_array
 
 pytestmark = pytest.mark.gpu
 
@@ -302,39 +302,50 @@ def test_raw_abi_unaligned_ragged(mode, baselines, context, command_queue):
     check_raw_abi(mode, 1, baselines, context, command_queue)
 
 
-def check_raw_abi(mode, offset, baselines, context, command_queue):
+def check_raw_abi(mode, offset, baselines, context, command_queue, views=None):
+    """`views` makes the arrays (tests/subviews.py: CompactViews unless given); the strides the
+    launchers get are those of the views it made."""
     from katsdpsigproc_amd import _lib
 
     queue = command_queue
+    views = views or CompactViews(context, queue)
     channels, cf = 6, 3
     dumps = make_dumps(np.random.RandomState(offset), channels, baselines, True, mode)
     strides = {"vis": 41, "flags": 39, "weights": 43, "mask": 45, "acc_vis": 37,
                "acc_weights": 47, "acc_flags": 49, "out_vis": 51, "out_weights": 37,
                "out_flags": 53}  # fmt: skip
     dtypes = {"vis": np.complex64, "weights": np.float32, "flags": np.uint8}
+
+    def make(name, dtype, data, poison=False):
+        made = views(name, dtype, data, strides[name], offset, poison)
+        strides[name] = made[0].stride
+        return made
+
     acc = {}
     for name in ACC:
-        acc[name] = flat_device_array(context, queue, dtypes[name[4:]],
-                                      np.zeros((channels, baselines), dtypes[name[4:]]),
-                                      strides[name], offset)  # fmt: skip
+        acc[name] = make(name, dtypes[name[4:]], np.zeros((channels, baselines), dtypes[name[4:]]))
     device_index = context.device.index
     stream = ctypes.c_void_p(queue.stream)
     for vis, flags, weights, mask in dumps:
-        d_vis = flat_device_array(context, queue, np.complex64, vis, strides["vis"], offset, poison=True)
-        d_flags = flat_device_array(context, queue, np.uint8, flags, strides["flags"], offset, poison=True)
-        d_weights = flat_device_array(context, queue, np.float32, weights, strides["weights"], offset, poison=True)
-        if mode == "CHANNEL":
-            d_mask = flat_device_array(context, queue, np.uint8, mask[np.newaxis, :], channels, offset, poison=True)
-        elif mode == "FULL":
-            d_mask = flat_device_array(context, queue, np.uint8, mask, strides["mask"], offset, poison=True)
-        else:
-            d_mask = (None, None)
-        _lib.call("ksp_average_accumulate", device_index, stream, d_vis[1], d_flags[1],
-                  d_weights[1], d_mask[1], modes()[mode].value, acc["acc_vis"][1],
-                  acc["acc_weights"][1], acc["acc_flags"][1], channels, baselines, strides["vis"],
-                  strides["flags"], strides["weights"], strides["mask"], strides["acc_vis"],
-                  strides["acc_weights"], strides["acc_flags"])  # fmt: skip
-        queue.finish()  # the inputs of this dump go out of scope
+        with views.scope():
+            d_vis = make("vis", np.complex64, vis, poison=True)
+            d_flags = make("flags", np.uint8, flags, poison=True)
+            d_weights = make("weights", np.float32, weights, poison=True)
+            if mode == "CHANNEL":
+                d_mask = flat_device_array(context, queue, np.uint8, mask[np.newaxis, :], channels, offset, poison=True)
+            elif mode == "FULL":
+                d_mask = make("mask", np.uint8, mask, poison=True)
+            else:
+                d_mask = (None, None)
+            _lib.call("ksp_average_accumulate", device_index, stream, d_vis[1], d_flags[1],
+                      d_weights[1], d_mask[1], modes()[mode].value, acc["acc_vis"][1],
+                      acc["acc_weights"][1], acc["acc_flags"][1], channels, baselines, strides["vis"],
+                      strides["flags"], strides["weights"], strides["mask"], strides["acc_vis"],
+                      strides["acc_weights"], strides["acc_flags"])  # fmt: skip
+            queue.finish()  # the inputs of this dump go out of scope
+            for name, view in (("vis", d_vis), ("flags", d_flags), ("weights", d_weights), ("mask", d_mask)):
+                if view[0] is not None:
+                    view[0].read(name)  # (asserts that nothing wrote to it)
     want_acc = host_accumulate(dumps, mode)
     for name, want in zip(ACC, want_acc):
         got = read_flat(queue, acc[name][0], (channels, baselines), strides[name], offset)
@@ -342,9 +353,7 @@ def check_raw_abi(mode, offset, baselines, context, command_queue):
     out = {}
     for name in OUT:
         dtype = dtypes[name]
-        out[name] = flat_device_array(
-            context, queue, dtype, sentinel_array((channels // cf, baselines), dtype),
-            strides["out_" + name], offset)  # fmt: skip
+        out[name] = make("out_" + name, dtype, sentinel_array((channels // cf, baselines), dtype))
     for clear in (0, 1):
         _lib.call("ksp_average_finalise", device_index, stream, acc["acc_vis"][1],
                   acc["acc_weights"][1], acc["acc_flags"][1], out["vis"][1], out["weights"][1],

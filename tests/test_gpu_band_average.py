@@ -9,7 +9,7 @@ import pytest
 
 from tests import inputs
 from tests import inputs_band_average as ba
-from tests.subviews import SENTINEL, flat_device_array, sentinel_array
+from tests.subviews import SENTINEL, CompactViews, flat_device_array, sentinel_array
 
 pytestmark = pytest.mark.gpu
 
@@ -183,10 +183,17 @@ def aligned_strides(baselines, channels):
 def test_raw_abi_subviews(offset, strides, use_flags, context, command_queue):
     """Pointers `offset` elements into their allocations and a stride of its own per array, odd
     ones and ones that keep the rows on 16 bytes: samples are loaded one by one either way."""
+    check_raw_abi(offset, strides, use_flags, context, command_queue)
+
+
+def check_raw_abi(offset, strides, use_flags, context, command_queue, views=None):
+    """`views` makes the arrays (tests/subviews.py: CompactViews unless given) and may choose
+    other strides of the same kind: the launcher gets the strides of the views."""
     from katsdpsigproc_amd import _lib
     from katsdpsigproc_amd.rfi import host
 
     queue = command_queue
+    views = views or CompactViews(context, queue)
     channels, baselines, n_series = 260, 333, 3
     mask = ba.MASK if use_flags else 0
     stride = dict(zip(STRIDE_NAMES, strides(baselines, channels)))
@@ -197,15 +204,17 @@ def test_raw_abi_subviews(offset, strides, use_flags, context, command_queue):
     padded_flags[:, :baselines] = ba.make_flags(offset + 1, (channels, baselines))
     padded_weights = hostile((n_series, stride["channel_weights"]), f32)
     padded_weights[:, :channels] = ba.make_weights(offset + 2, n_series, channels)
-    d_data = flat_device_array(context, queue, c64, padded, stride["data"], offset, poison=True)
-    d_flags = flat_device_array(context, queue, np.uint8, padded_flags, stride["flags"], offset,
-                                poison=True)  # fmt: skip
-    d_weights = flat_device_array(context, queue, f32, padded_weights, stride["channel_weights"],
-                                  offset, poison=True)  # fmt: skip
+
+    def make(name, dtype, data, poison=False):
+        made = views(name, dtype, data, stride[name], offset, poison)
+        stride[name] = made[0].stride
+        return made
+
+    d_data = make("data", c64, padded, poison=True)
+    d_flags = make("flags", np.uint8, padded_flags, poison=True)
+    d_weights = make("channel_weights", f32, padded_weights, poison=True)
     dtypes = dict(zip(NAMES, (c64, f32, f32, np.uint32, np.uint8)))
-    out = {name: flat_device_array(context, queue, dtypes[name],
-                                   sentinel_array((n_series, baselines), dtypes[name]),
-                                   stride[name], offset)
+    out = {name: make(name, dtypes[name], sentinel_array((n_series, baselines), dtypes[name]))
            for name in NAMES}  # fmt: skip
     work_bytes = _lib.load().ksp_band_average_work_bytes(channels, baselines, n_series)
     assert work_bytes == 3 * n_series * 5 * baselines * 4

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from tests import inputs
-from tests.subviews import SENTINEL, flat_device_array, sentinel_array
+from tests.subviews import SENTINEL, CompactViews, flat_device_array, sentinel_array
 
 pytestmark = pytest.mark.gpu
 
@@ -278,23 +278,29 @@ def test_raw_abi_subviews(offset, strides, channels, baselines, context, command
     array. Odd strides take the element-wise path; 16 elements and strides that keep the rows
     on 16 bytes take the 16-byte path from the middle of an allocation; 4 elements with such
     strides leave `weights` on 16 bytes and `weights8` off them: 16-byte loads, single stores."""
+    check_raw_abi(offset, strides, channels, baselines, context, command_queue)
+
+
+def check_raw_abi(offset, strides, channels, baselines, context, command_queue, views=None):
+    """`views` makes the strided arrays (tests/subviews.py: CompactViews unless given) and may
+    choose other strides of the same kind."""
     from katsdpsigproc_amd import _lib
     from katsdpsigproc_amd.rfi import host
 
     queue = command_queue
+    views = views or CompactViews(context, queue)
     weights, columns = make_weights(offset + baselines, channels, baselines, offset)
     weights_stride, weights8_stride = strides(baselines)
     # the rows with their padding as data of the view: 2^127 and NaN, NaN all around it
     padded = hostile_padding((channels, weights_stride))
     padded[:, :baselines] = weights
-    d_in = flat_device_array(context, queue, f32, padded, weights_stride, offset, poison=True)
-    d_out = flat_device_array(context, queue, np.uint8,
-                              sentinel_array((channels, baselines), np.uint8), weights8_stride,
-                              offset)  # fmt: skip
+    d_in = views("weights", f32, padded, weights_stride, offset, poison=True)
+    d_out = views("weights8", np.uint8, sentinel_array((channels, baselines), np.uint8),
+                  weights8_stride, offset)  # fmt: skip
     d_wc = flat_device_array(context, queue, f32, sentinel_array((1, channels), f32), channels,
                              offset)  # fmt: skip
     _lib.call("ksp_compress_weights", context.device.index, ctypes.c_void_p(queue.stream),
-              d_in[1], d_out[1], d_wc[1], channels, baselines, weights_stride, weights8_stride)
+              d_in[1], d_out[1], d_wc[1], channels, baselines, d_in[0].stride, d_out[0].stride)
     want = host.CompressWeightsHost()(weights)
     assert_same(want[1], d_wc[0].read("weights_channel")[0], f"weights_channel at {offset}")
     assert_same(want[0], d_out[0].read("weights8"), f"weights8 at {offset}")

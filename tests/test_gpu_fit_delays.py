@@ -11,7 +11,7 @@ import pytest
 
 from tests import inputs_fit_delays as gen
 from tests.inputs_fit_delays import assert_same
-from tests.subviews import flat_device_array, poison_array, sentinel_array
+from tests.subviews import CompactViews, poison_array, sentinel_array
 from tests.test_gpu_prepare import LOST, N_AUTO
 
 pytestmark = pytest.mark.gpu
@@ -202,24 +202,32 @@ def test_padding(channels, n_inputs, n_fft, pad, context, command_queue):
 def test_raw_abi_subviews(offset, channels, n_inputs, n_fft, context, command_queue):
     """Sub-views: pointers `offset` elements into their allocations and an odd stride of its own
     for gains and model; the variants rotate."""
+    check_raw_abi(offset, channels, n_inputs, n_fft, context, command_queue)
+
+
+def check_raw_abi(offset, channels, n_inputs, n_fft, context, command_queue, views=None,
+                  variant=None):
+    """`views` makes the arrays (tests/subviews.py: CompactViews unless given) and may choose
+    other strides of the same kind; `variant` instead of the one that is due by rotation."""
     from katsdpsigproc_amd import _lib
 
     queue = command_queue
+    views = views or CompactViews(context, queue)
     seed = 31 * offset + n_inputs
-    with_status, with_model, corrections = VARIANTS[seed % 8]
+    with_status, with_model, corrections = variant or VARIANTS[seed % 8]
     key = (seed, channels, n_inputs, n_fft, seed)
     gains, status, _ = cached_case(*key)
     want = cached_want(key, n_fft, 2, with_status, corrections, 1e5)
 
-    def view(data, stride, poison):
-        return flat_device_array(context, queue, data.dtype, data, stride, offset, poison=poison)
+    def view(name, data, stride, poison):
+        return views(name, data.dtype, data, stride, offset, poison=poison)
 
     def blank(name, shape):
-        return view(sentinel_array(shape, DTYPES[name]), shape[1] if shape[0] == 1 else
+        return view(name, sentinel_array(shape, DTYPES[name]), shape[1] if shape[0] == 1 else
                     (n_inputs + 8) | 1, False)  # fmt: skip
 
-    d_gains = view(gains, (n_inputs + 4) | 1, True)
-    d_status = view(status[np.newaxis, :], channels, True) if with_status else None
+    d_gains = view("gains", gains, (n_inputs + 4) | 1, True)
+    d_status = view("status", status[np.newaxis, :], channels, True) if with_status else None
     d_out = {name: blank(name, (1, n_inputs)) for name in OUTPUTS[:4]}
     if with_model:
         d_out["model"] = blank("model", (channels, n_inputs))

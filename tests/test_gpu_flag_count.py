@@ -119,21 +119,21 @@ def test_padding(rows, cols, context, command_queue):
     check(context, command_queue, flags, (0x0F, 0x80), pad=29, transposed=True)
 
 
-def call_abi(context, queue, flags, stride, offset, masks=(0xFF,)):
+def call_abi(context, queue, flags, stride, offset, masks=(0xFF,), views=None):
     """ksp_flag_count on `flags` laid out with `stride` bytes per row, starting `offset`
-    bytes into an allocation; the outputs have stride rows + 3 / cols + 5."""
+    bytes into an allocation; the outputs have stride rows + 3 / cols + 5. `views` makes the
+    arrays (subviews.CompactViews unless given) and may choose other strides."""
     from katsdpsigproc_amd import _lib
 
+    views = views or subviews.CompactViews(context, queue)
     rows, cols = flags.shape
-    dev_in = subviews.DeviceView(context, queue, np.uint8, flags, stride, offset, poison=True)
+    dev_in = views("flags", np.uint8, flags, stride, offset, poison=True)[0]
     blank = subviews.sentinel_array  # (counts start as sentinels: the launcher overwrites them)
-    row_out = subviews.DeviceView(context, queue, np.uint32, blank((len(masks), rows), np.uint32),
-                                  rows + 3)  # fmt: skip
-    col_out = subviews.DeviceView(context, queue, np.uint32, blank((len(masks), cols), np.uint32),
-                                  cols + 5)  # fmt: skip
+    row_out = views("row_counts", np.uint32, blank((len(masks), rows), np.uint32), rows + 3)[0]
+    col_out = views("col_counts", np.uint32, blank((len(masks), cols), np.uint32), cols + 5)[0]
     _lib.call("ksp_flag_count", context.device.index, ctypes.c_void_p(queue.stream),
-              dev_in.ptr, row_out.ptr, col_out.ptr, rows, cols, stride, rows + 3, cols + 5,
-              (ctypes.c_uint8 * len(masks))(*masks), len(masks), 0)  # fmt: skip
+              dev_in.ptr, row_out.ptr, col_out.ptr, rows, cols, dev_in.stride, row_out.stride,
+              col_out.stride, (ctypes.c_uint8 * len(masks))(*masks), len(masks), 0)  # fmt: skip
     dev_in.read("flags")
     return row_out.read("row_counts"), col_out.read("col_counts")
 

@@ -10,7 +10,7 @@ import pytest
 
 from tests import inputs_predict as gen
 from tests.inputs_predict import assert_same
-from tests.subviews import flat_device_array, poison_array, sentinel_array
+from tests.subviews import CompactViews, poison_array, sentinel_array
 from tests.test_gpu_prepare import LOST, N_AUTO
 
 pytestmark = pytest.mark.gpu
@@ -222,35 +222,46 @@ def test_raw_abi_subviews(offset, strides, channels, baselines, n_sources, conte
     element-wise path; 16 elements and strides that keep the rows on 16 bytes take the 16-byte
     path from the middle of an allocation; 4 elements with such strides leave the flags off 16
     bytes. The variants rotate; in place and out of place both."""
+    check_raw_abi(offset, strides, channels, baselines, n_sources, context, command_queue)
+
+
+def check_raw_abi(offset, strides, channels, baselines, n_sources, context, command_queue,
+                  views=None, variant=None):
+    """`views` makes the arrays (tests/subviews.py: CompactViews unless given) and may choose
+    other strides of the same kind; `variant` instead of the one that is due by rotation."""
     from katsdpsigproc_amd import _lib
 
     queue = command_queue
+    views = views or CompactViews(context, queue)
     seed = 31 * offset + baselines
-    model, divide, weights, flags, _ = VARIANTS[seed % 9]
+    model, divide, weights, flags, _ = variant or VARIANTS[seed % 9]
     case, want = cached(seed, channels, baselines, n_sources, gen.PATTERNS[seed % 7])
     delays_stride, flux_stride, data_strides = strides(baselines, n_sources)
     kinds = [kind for kind, there in zip(KINDS, (divide, weights, flags)) if there]
     stride_of = dict(zip(("model",) + KINDS + tuple("out_" + kind for kind in KINDS), data_strides))
 
-    def view(data, stride, poison):
-        return flat_device_array(context, queue, data.dtype, data, stride, offset, poison=poison)
+    def view(name, data, stride, poison):
+        return views(name, data.dtype, data, stride, offset, poison=poison)
 
-    d_freqs = view(case["freqs"][np.newaxis, :], channels, True)
-    d_delays = view(case["delays"], delays_stride, True)
-    d_flux = view(case["flux"], flux_stride, True)
+    d_freqs = view("freqs", case["freqs"][np.newaxis, :], channels, True)
+    d_delays = view("delays", case["delays"], delays_stride, True)
+    d_flux = view("flux", case["flux"], flux_stride, True)
+    mark = views.mark()
     for in_place in (False, True) if divide else (False,):
+        views.release(mark)  # (the arrays of the round before)
         d_in, d_out = {}, {}
         if model:
             blank = sentinel_array((channels, baselines), np.complex64)
-            d_out["model"] = view(blank, stride_of["model"], False)
+            d_out["model"] = view("model", blank, stride_of["model"], False)
         for kind in kinds:
             # in place the array is an output: sentinels around it instead of poison
-            d_in[kind] = view(case[kind], stride_of[kind], not in_place)
+            d_in[kind] = view(("out_" if in_place else "") + kind, case[kind], stride_of[kind],
+                              not in_place)  # fmt: skip
             if in_place:
                 d_out[kind] = d_in[kind]
             else:
                 blank = sentinel_array((channels, baselines), DTYPES[kind])
-                d_out[kind] = view(blank, stride_of["out_" + kind], False)
+                d_out[kind] = view("out_" + kind, blank, stride_of["out_" + kind], False)
 
         def ptr(views, kind):
             return views[kind][1] if kind in views else None
@@ -262,7 +273,7 @@ def test_raw_abi_subviews(offset, strides, channels, baselines, n_sources, conte
                   d_freqs[1], d_delays[1], d_flux[1], ptr(d_out, "model"), ptr(d_in, "vis"),
                   ptr(d_in, "weights"), ptr(d_in, "flags"), ptr(d_out, "vis"),
                   ptr(d_out, "weights"), ptr(d_out, "flags"), channels, baselines, n_sources,
-                  delays_stride, flux_stride, stride(d_out, "model"), stride(d_in, "vis"),
+                  d_delays[0].stride, d_flux[0].stride, stride(d_out, "model"), stride(d_in, "vis"),
                   stride(d_in, "weights"), stride(d_in, "flags"), stride(d_out, "vis"),
                   stride(d_out, "weights"), stride(d_out, "flags"), 64)  # fmt: skip
         what = f"at {offset}, in place {in_place}"

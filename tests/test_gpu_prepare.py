@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from tests import inputs
-from tests.subviews import SENTINEL, flat_device_array, sentinel_array
+from tests.subviews import SENTINEL, CompactViews, flat_device_array, sentinel_array
 
 pytestmark = pytest.mark.gpu
 
@@ -277,10 +277,23 @@ def test_raw_abi_subviews_ragged(offset, strides, baselines, variant, context, c
     check_raw_abi(offset, strides, variant, baselines, True, context, command_queue)
 
 
-def check_raw_abi(offset, strides, variant, baselines, invalid_last, context, command_queue):
+def check_raw_abi(offset, strides, variant, baselines, invalid_last, context, command_queue,
+                  views=None):
+    """`views` makes the strided arrays (tests/subviews.py: CompactViews unless given) and may
+    choose other strides of the same kind."""
     from katsdpsigproc_amd import _lib
 
     queue = command_queue
+    views = views or CompactViews(context, queue)
+    # vis_in as rows of int32: a pair stride of n is a row stride of 2 n words
+    strides = dict(strides, vis_in=2 * strides["vis_in"])
+
+    def make(name, dtype, data, poison=False):
+        """(view, pointer); the stride the launcher gets is the one the view was made with"""
+        made = views(name, dtype, data, strides[name], offset, poison)
+        strides[name] = made[0].stride
+        return made
+
     channels, in_baselines = 6, 21
     use_mask, use_weights = variant
     case = list(make_case(offset, channels, baselines, in_baselines, "permutation"))
@@ -288,9 +301,8 @@ def check_raw_abi(offset, strides, variant, baselines, invalid_last, context, co
         case[1][-1] = in_baselines
         case[3][-1] = [-1, 2**31 - 1]
     vis_in, source, channel_flags, auto_source = case
-    # vis_in as rows of int32: a pair stride of n is a row stride of 2 n words
-    d_in = flat_device_array(context, queue, np.int32, vis_in.reshape(channels, -1),
-                             2 * strides["vis_in"], offset, poison=True)  # fmt: skip
+    d_in = make("vis_in", np.int32, vis_in.reshape(channels, -1), poison=True)
+    assert strides["vis_in"] % 2 == 0
     d_source = flat_device_array(context, queue, np.int32, source[np.newaxis, :], baselines,
                                  offset, poison=True)  # fmt: skip
     d_auto = flat_device_array(context, queue, np.int32, auto_source.reshape(1, -1),
@@ -298,14 +310,13 @@ def check_raw_abi(offset, strides, variant, baselines, invalid_last, context, co
     d_mask = flat_device_array(context, queue, np.uint8, channel_flags[np.newaxis, :], channels,
                                offset, poison=True)  # fmt: skip
     dtypes = {"vis": np.complex64, "input_flags": np.uint8, "weights": np.float32}
-    out = {name: flat_device_array(context, queue, dtype,
-                                   sentinel_array((channels, baselines), dtype), strides[name], offset)
+    out = {name: make(name, dtype, sentinel_array((channels, baselines), dtype))
            for name, dtype in dtypes.items()}  # fmt: skip
     null = ctypes.c_void_p(0)
     _lib.call("ksp_prepare", context.device.index, ctypes.c_void_p(queue.stream), d_in[1],
               d_source[1], d_auto[1] if use_weights else null, d_mask[1] if use_mask else null,
               out["vis"][1], out["input_flags"][1], out["weights"][1] if use_weights else null,
-              channels, in_baselines, baselines, strides["vis_in"], strides["vis"],
+              channels, in_baselines, baselines, strides["vis_in"] // 2, strides["vis"],
               strides["input_flags"], strides["weights"], 2.0**-8, 2.0**20, 0x10)  # fmt: skip
     want = run_host(case, variant, scale=2.0**-8, lost_flag=0x10, weight_scale=2.0**20)
     for name, w in zip(dtypes, want):

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from tests import inputs
-from tests.subviews import SENTINEL, flat_device_array, sentinel_array
+from tests.subviews import SENTINEL, CompactViews, flat_device_array, sentinel_array
 from tests.test_gpu_prepare import (N_AUTO, assert_same, chain_dump, make_case, read_checked,
                                     write_padded)  # fmt: skip
 
@@ -199,11 +199,30 @@ def test_raw_abi_subviews(flag_offset, offset, strides, classes, use_baseline_fl
     other arrays `offset` elements into theirs, a stride of its own per array and an odd one
     for the rows of `channel_flags`. 37 baselines: two whole runs and a ragged one, with
     indices outside the input and outside the classes in the last baselines."""
+    check_raw_abi(flag_offset, offset, strides, classes, use_baseline_flags, use_weights,
+                  context, command_queue)  # fmt: skip
+
+
+def check_raw_abi(flag_offset, offset, strides, classes, use_baseline_flags, use_weights,
+                  context, command_queue, views=None):  # fmt: skip
+    """`views` makes the strided arrays (tests/subviews.py: CompactViews unless given) and may
+    choose other strides of the same kind."""
     from katsdpsigproc_amd import _lib
     from katsdpsigproc_amd.rfi import host
 
     queue = command_queue
+    views = views or CompactViews(context, queue)
     channels, in_baselines, baselines = 6, 21, 37
+    # vis_in as rows of int32: a pair stride of n is a row stride of 2 n words; the rows of
+    # channel_flags have an odd stride, 7
+    strides = dict(strides, vis_in=2 * strides["vis_in"], channel_flags=channels + 1)
+
+    def make(name, dtype, data, poison=False):
+        """(view, pointer); the stride the launcher gets is the one the view was made with"""
+        made = views(name, dtype, data, strides[name], offset, poison)
+        strides[name] = made[0].stride
+        return made
+
     case = list(make_case(offset, channels, baselines, in_baselines, "permutation"))
     case[1][-1] = in_baselines
     case[3][-1] = [-1, 2**31 - 1]
@@ -211,30 +230,27 @@ def test_raw_abi_subviews(flag_offset, offset, strides, classes, use_baseline_fl
     arguments = host_arguments(case, flags, classes, use_baseline_flags, use_weights)
     vis_in, source, masks, _, _, _ = arguments
     auto_source, (_, index, baseline_flags) = case[3], flags
-    d_in = flat_device_array(context, queue, np.int32, vis_in.reshape(channels, -1),
-                             2 * strides["vis_in"], offset, poison=True)  # fmt: skip
+    d_in = make("vis_in", np.int32, vis_in.reshape(channels, -1), poison=True)
+    assert strides["vis_in"] % 2 == 0
     d_source = flat_device_array(context, queue, np.int32, source[np.newaxis, :], baselines,
                                  offset, poison=True)  # fmt: skip
     d_auto = flat_device_array(context, queue, np.int32, auto_source.reshape(1, -1),
                                2 * baselines, offset, poison=True)  # fmt: skip
-    mask_stride = channels + 1  # 7: odd
-    d_masks = flat_device_array(context, queue, u8, np.atleast_2d(masks), mask_stride, offset,
-                                poison=True)  # fmt: skip
+    d_masks = make("channel_flags", u8, np.atleast_2d(masks), poison=True)
     d_index = flat_device_array(context, queue, u8, (index if classes else baseline_flags)[np.newaxis, :],
                                 baselines, flag_offset, poison=True)  # fmt: skip
     d_flags = flat_device_array(context, queue, u8, baseline_flags[np.newaxis, :], baselines,
                                 flag_offset, poison=True)  # fmt: skip
     dtypes = {"vis": np.complex64, "input_flags": u8, "weights": np.float32}
-    out = {name: flat_device_array(context, queue, dtype,
-                                   sentinel_array((channels, baselines), dtype), strides[name], offset)
+    out = {name: make(name, dtype, sentinel_array((channels, baselines), dtype))
            for name, dtype in dtypes.items()}  # fmt: skip
     null = ctypes.c_void_p(0)
     _lib.call("ksp_prepare_flags", context.device.index, ctypes.c_void_p(queue.stream), d_in[1],
               d_source[1], d_auto[1] if use_weights else null, d_masks[1],
               d_index[1] if classes else null, d_flags[1] if use_baseline_flags else null,
               out["vis"][1], out["input_flags"][1], out["weights"][1] if use_weights else null,
-              channels, in_baselines, baselines, classes, strides["vis_in"],
-              mask_stride if classes else 0, strides["vis"], strides["input_flags"],
+              channels, in_baselines, baselines, classes, strides["vis_in"] // 2,
+              strides["channel_flags"] if classes else 0, strides["vis"], strides["input_flags"],
               strides["weights"], 2.0**-8, 2.0**20, 0x10)  # fmt: skip
     want = host.PrepareHost(2.0**-8, 0x10, 2.0**20)(*arguments)
     for name, w in zip(dtypes, want):

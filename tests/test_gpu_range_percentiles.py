@@ -9,7 +9,7 @@ import pytest
 
 from tests import inputs
 from tests import inputs_range_percentiles as rp
-from tests.subviews import SENTINEL, flat_device_array, sentinel_array
+from tests.subviews import SENTINEL, CompactViews, sentinel_array
 
 pytestmark = pytest.mark.gpu
 
@@ -244,10 +244,17 @@ def test_raw_abi_subviews(offset, strides, use_flags, dtype, context, command_qu
     """Pointers `offset` elements into their allocations and a stride of its own per array:
     odd strides take the element-wise path in most rows, 16 elements with strides that keep the
     rows on 16 bytes take the 16-byte loads where a range starts on one."""
+    check_raw_abi(offset, strides, use_flags, dtype, context, command_queue)
+
+
+def check_raw_abi(offset, strides, use_flags, dtype, context, command_queue, views=None):
+    """`views` makes the arrays (tests/subviews.py: CompactViews unless given) and may choose
+    other strides of the same kind: the launcher gets the strides of the views."""
     from katsdpsigproc_amd import _lib
     from katsdpsigproc_amd.rfi import host
 
     queue = command_queue
+    views = views or CompactViews(context, queue)
     channels, baselines = 6, 2500
     ranges = [(0, 64), (64, 321), (4, 2400), (321, 321), (7, 2500), (2436, 2500)]
     mask = 0x01 if use_flags else 0
@@ -257,14 +264,18 @@ def test_raw_abi_subviews(offset, strides, use_flags, dtype, context, command_qu
     padded[:, :baselines] = rp.make_data(offset, channels, baselines, dtype)
     padded_flags = hostile((channels, stride["flags"]), np.uint8)
     padded_flags[:, :baselines] = rp.make_flags(offset + 1, (channels, baselines))
-    d_data = flat_device_array(context, queue, dtype, padded, stride["data"], offset, poison=True)
-    d_flags = flat_device_array(context, queue, np.uint8, padded_flags, stride["flags"], offset,
-                                poison=True)  # fmt: skip
+
+    def make(name, dtype, data, poison=False):
+        made = views(name, dtype, data, stride[name], offset, poison)
+        stride[name] = made[0].stride
+        return made
+
+    d_data = make("data", dtype, padded, poison=True)
+    d_flags = make("flags", np.uint8, padded_flags, poison=True)
     n = len(ranges)
     shapes = {"percentiles": (5 * n, channels), "counts": (n, channels), "range_flags": (n, channels)}
     dtypes = {"percentiles": f32, "counts": np.uint32, "range_flags": np.uint8}
-    out = {name: flat_device_array(context, queue, dtypes[name],
-                                   sentinel_array(shapes[name], dtypes[name]), stride[name], offset)
+    out = {name: make(name, dtypes[name], sentinel_array(shapes[name], dtypes[name]))
            for name in NAMES}  # fmt: skip
     null = ctypes.c_void_p(0)
     _lib.call("ksp_range_percentiles", context.device.index, ctypes.c_void_p(queue.stream),

@@ -229,14 +229,16 @@ def test_masks(mask, flag_value, context, command_queue):
     assert (want != flags).any()
 
 
-def call_abi(context, queue, data, stride, offset, axis, eta_q, mask=0xFF, flag_value=1):
+def call_abi(context, queue, data, stride, offset, axis, eta_q, mask=0xFF, flag_value=1,
+             views=None):
     """ksp_sir on `data` (as it lies in memory) with `stride` bytes per row, `offset` bytes
-    into an allocation full of sentinels (0xAB: flags that must not count)."""
+    into an allocation full of sentinels (0xAB: flags that must not count). `views` makes the
+    array (subviews.CompactViews unless given) and may choose another stride."""
     from katsdpsigproc_amd import _lib
 
-    view = subviews.DeviceView(context, queue, np.uint8, data, stride, offset)
+    view = (views or subviews.CompactViews(context, queue))("flags", np.uint8, data, stride, offset)[0]
     _lib.call("ksp_sir", context.device.index, ctypes.c_void_p(queue.stream), view.ptr,
-              data.shape[0], data.shape[1], stride, axis, eta_q, mask, flag_value)  # fmt: skip
+              data.shape[0], data.shape[1], view.stride, axis, eta_q, mask, flag_value)  # fmt: skip
     return view.read("flags")
 
 

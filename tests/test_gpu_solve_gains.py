@@ -12,7 +12,7 @@ import pytest
 
 from tests import inputs_solve_gains as gen
 from tests.inputs_solve_gains import assert_same
-from tests.subviews import flat_device_array, poison_array, sentinel_array
+from tests.subviews import CompactViews, poison_array, sentinel_array
 from tests.test_gpu_prepare import LOST, N_AUTO
 
 pytestmark = pytest.mark.gpu
@@ -253,12 +253,20 @@ def test_padding(n_inputs, channels, pad, context, command_queue):
 def test_raw_abi_subviews(offset, channels, n_inputs, extra, context, command_queue):
     """Sub-views: pointers `offset` elements into their allocations and an odd stride of its own
     per array; the variants rotate; gains apart from initial and in place."""
+    check_raw_abi(offset, channels, n_inputs, extra, context, command_queue)
+
+
+def check_raw_abi(offset, channels, n_inputs, extra, context, command_queue, views=None,
+                  variant=None):
+    """`views` makes the arrays (tests/subviews.py: CompactViews unless given) and may choose
+    other strides of the same kind; `variant` instead of the one that is due by rotation."""
     from katsdpsigproc_amd import _lib
     from katsdpsigproc_amd.rfi import host
 
     queue = command_queue
+    views = views or CompactViews(context, queue)
     seed = 31 * offset + n_inputs
-    variant = VARIANTS[seed % len(VARIANTS)]
+    variant = variant or VARIANTS[seed % len(VARIANTS)]
     case = cached_case(seed, channels, n_inputs, gen.TABLES[seed % 5], "hostile", extra)
     given = given_of(case, variant)
     baselines = case["vis"].shape[1]
@@ -268,23 +276,26 @@ def test_raw_abi_subviews(offset, channels, n_inputs, extra, context, command_qu
                  "flags": (baselines + 4) | 1, "pairs": (n_inputs + 2) | 1,
                  "initial": (n_inputs + 4) | 1, "gains": (n_inputs + 8) | 1}  # fmt: skip
 
-    def view(data, stride, poison):
-        return flat_device_array(context, queue, data.dtype, data, stride, offset, poison=poison)
+    def view(name, data, stride, poison):
+        return views(name, data.dtype, data, stride, offset, poison=poison)
 
-    inputs = {name: view(value, stride_of[name], True)
+    inputs = {name: view(name, value, stride_of[name], True)
               for name, value in given.items() if value is not None and name != "initial"}  # fmt: skip
+    mark = views.mark()
     for in_place in (False, True) if given["initial"] is not None else (False,):
+        views.release(mark)  # (the arrays of the round before)
         d_initial = None
         if given["initial"] is not None:
             # in place the array is an output: sentinels around it instead of poison
-            d_initial = view(given["initial"], stride_of["initial"], not in_place)
+            d_initial = view("gains" if in_place else "initial", given["initial"],
+                             stride_of["initial"], not in_place)  # fmt: skip
         if in_place:
             d_gains = d_initial
         else:
             blank = sentinel_array((channels, n_inputs), np.complex64)
-            d_gains = view(blank, stride_of["gains"], False)
-        d_iterations = view(sentinel_array((1, channels), np.int32), channels, False)
-        d_status = view(sentinel_array((1, channels), np.uint8), channels, False)
+            d_gains = view("gains", blank, stride_of["gains"], False)
+        d_iterations = view("iterations", sentinel_array((1, channels), np.int32), channels, False)
+        d_status = view("status", sentinel_array((1, channels), np.uint8), channels, False)
 
         def ptr(name):
             return inputs[name][1] if name in inputs else None

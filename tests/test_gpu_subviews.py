@@ -58,19 +58,30 @@ class Gpu:
         self.device = context.device.index
         self.stream = ctypes.c_void_p(queue.stream)
 
-    def input(self, data, stride=None, offset=0):
-        """`data` (1-D: a single row) in poison; read() checks that it was left alone."""
+    def input(self, data, stride=None, offset=0, role=None):
+        """`data` (1-D: a single row) in poison; read() checks that it was left alone. `role`
+        names the argument of the launcher that the view becomes."""
         data = np.atleast_2d(data)
         stride = data.shape[1] if stride is None else stride
-        return subviews.DeviceView(self.context, self.queue, data.dtype, data, stride, offset,
-                                   poison=True)  # fmt: skip
+        return self.view(data.dtype, data, stride, offset, True, role)
 
-    def output(self, shape, dtype, stride=None, offset=0):
+    def output(self, shape, dtype, stride=None, offset=0, role=None):
         """An array of sentinels among sentinels; read() checks everything around the rows."""
         shape = (1, shape) if np.isscalar(shape) else tuple(shape)
         stride = shape[1] if stride is None else stride
         blank = subviews.sentinel_array(shape, dtype)
-        return subviews.DeviceView(self.context, self.queue, dtype, blank, stride, offset)
+        return self.view(dtype, blank, stride, offset, False, role)
+
+    def view(self, dtype, data, stride, offset, poison, role):
+        """The view factory: compact sub-views here, whatever the role. The bodies below take
+        the strides they hand to a launcher from the views (or from :meth:`shared_stride`), so
+        that another factory (tests/test_gpu_far_rows.py) may choose other strides."""
+        return subviews.DeviceView(self.context, self.queue, dtype, data, stride, offset, poison)
+
+    def shared_stride(self, like, arrays):
+        """The one stride of `arrays`, (role, rows, cols, dtype) each, that a launcher takes
+        for several arrays at once: `like`, the compact stride, here."""
+        return like
 
     def call(self, name, *args):
         return _lib.call(name, self.device, self.stream, *args)
@@ -121,11 +132,17 @@ def test_transpose(elem_size, gpu):
         want = np.ascontiguousarray(data.T)
         for name, odd, src_offset, dst_offset in TRANSPOSE_CASES:
             what = f"{rows} x {cols} x {elem_size} B, case {name}"
-            src = gpu.input(data, row_stride(cols, odd), src_offset)
-            dst = gpu.output((cols, rows), dtype, row_stride(rows, odd, 1), dst_offset)
-            gpu.call("ksp_transpose", dst.ptr, src.ptr, rows, cols, dst.stride, src.stride, elem_size)
-            assert_equal(want, dst.read("dst, " + what), what)
-            src.read("src, " + what)
+            run_transpose(gpu, data, want, odd, src_offset, dst_offset, what)
+
+
+def run_transpose(gpu, data, want, odd, src_offset, dst_offset, what):
+    rows, cols = data.shape
+    src = gpu.input(data, row_stride(cols, odd), src_offset, role="in")
+    dst = gpu.output((cols, rows), data.dtype, row_stride(rows, odd, 1), dst_offset, role="out")
+    gpu.call("ksp_transpose", dst.ptr, src.ptr, rows, cols, dst.stride, src.stride,
+             data.dtype.itemsize)  # fmt: skip
+    assert_equal(want, dst.read("dst, " + what), what)
+    src.read("src, " + what)
 
 
 # ----------------------------------------------------------------------------- percentile5
@@ -157,10 +174,10 @@ def p5_run(gpu, data, want, first_col, in_stride, in_offset, is_amplitude, what)
     rows, n_cols = data.shape
     # the rows of the call start first_col elements in front of the data: those columns, like
     # the ones behind the range, are poison
-    src = gpu.input(data, in_stride, in_offset + first_col)
+    src = gpu.input(data, in_stride, in_offset + first_col, role="in")
     base = ctypes.c_void_p(src.address - first_col * data.dtype.itemsize)
-    out = gpu.output((5, rows), F32, rows + 3)
-    gpu.call("ksp_percentile5_float", base, out.ptr, rows, in_stride, out.stride, first_col,
+    out = gpu.output((5, rows), F32, rows + 3, role="out")
+    gpu.call("ksp_percentile5_float", base, out.ptr, rows, src.stride, out.stride, first_col,
              n_cols, int(is_amplitude))  # fmt: skip
     assert_equal(want, out.read("out, " + what), what)
     src.read("in, " + what)
@@ -235,11 +252,18 @@ def test_madnz_t(baselines, gpu, oracle):
         data = np.ascontiguousarray(dev.T)
         for name, odd, in_offset, _ in cases("ABCE"):
             what = f"{channels} channels, {baselines} baselines, case {name}"
-            src = gpu.input(data, row_stride(channels, odd), in_offset)
-            noise = gpu.output(baselines, F32, offset=int(name != "A"))
-            gpu.call("ksp_madnz_t", src.ptr, noise.ptr, channels, baselines, src.stride)
-            assert_equal(want[np.newaxis], noise.read("noise, " + what), what)
-            src.read("in, " + what)
+            run_madnz(gpu, "ksp_madnz_t", data, want, row_stride(channels, odd), in_offset,
+                      int(name != "A"), what)  # fmt: skip
+
+
+def run_madnz(gpu, launcher, data, want, stride, in_offset, out_offset, what):
+    """ksp_madnz_t on data [B][stride], ksp_madnz on data [C][stride]."""
+    channels, baselines = data.shape[::-1] if launcher == "ksp_madnz_t" else data.shape
+    src = gpu.input(data, stride, in_offset, role="in")
+    noise = gpu.output(baselines, F32, offset=out_offset)
+    gpu.call(launcher, src.ptr, noise.ptr, channels, baselines, src.stride)
+    assert_equal(want[np.newaxis], noise.read("noise, " + what), what)
+    src.read("in, " + what)
 
 
 # the strip kernel (up to 4096 channels): 8 baselines per workgroup, loaded four at a time
@@ -254,11 +278,8 @@ def test_madnz(channels, baselines, gpu, oracle):
     dev, want = noise_case(rs, oracle, channels, baselines)
     for name, odd, in_offset, _ in cases("ABCE"):
         what = f"{channels} channels, {baselines} baselines, case {name}"
-        src = gpu.input(dev, row_stride(baselines, odd), in_offset)
-        noise = gpu.output(baselines, F32, offset=int(name != "A"))
-        gpu.call("ksp_madnz", src.ptr, noise.ptr, channels, baselines, src.stride)
-        assert_equal(want[np.newaxis], noise.read("noise, " + what), what)
-        src.read("in, " + what)
+        run_madnz(gpu, "ksp_madnz", dev, want, row_stride(baselines, odd), in_offset,
+                  int(name != "A"), what)  # fmt: skip
 
 
 # ---------------------------------------------------------------------- threshold_simple
@@ -269,39 +290,61 @@ SIMPLE_COLS = [1, 3, 4, 5, 1023, 1024, 1025, 1027]  # a lane owns 4 columns, a w
 def test_threshold_simple(transposed, gpu, oracle):
     """deviations and flags share one stride; the 16-byte loads need aligned deviations and the
     4-byte stores aligned flags, which is checked separately (case D moves the flags alone)."""
-    n_sigma, flag_value = 11.0, 4
     rs = np.random.RandomState(int(transposed))
     flagged = total = 0
     for rows in (1, 3):
         for cols in SIMPLE_COLS:
-            channels, baselines = (cols, rows) if transposed else (rows, cols)
-            noise = rs.uniform(5.0, 15.0, baselines).astype(F32)
-            limit = np.broadcast_to(F32(n_sigma) * noise, (channels, baselines))  # float32 product
-            # about half above the limit; some exactly on it (not flagged: the comparison is a
-            # strict >) and some one float32 above it
-            dev = (limit * rs.uniform(0.0, 2.0, limit.shape)).astype(F32)
-            pick = rs.random_sample(limit.shape)
-            exact, above = pick < 0.15, (pick >= 0.15) & (pick < 0.3)
-            dev[exact] = limit[exact]
-            dev[above] = np.nextafter(limit[above], F32(np.inf))
-            want = oracle.ThresholdSimpleHost(n_sigma, flag_value)(dev, noise)
-            assert not want[exact].any() and np.all(want[above] == flag_value)
+            dev, noise, want = simple_case(rs, oracle, rows, cols, transposed)
             flagged += np.count_nonzero(want)
             total += want.size
-            if transposed:
-                dev, want = np.ascontiguousarray(dev.T), np.ascontiguousarray(want.T)
             for name, odd, in_offset, out_offset in cases("ABCDE"):
                 what = f"{rows} x {cols}, transposed {transposed}, case {name}"
-                stride = row_stride(cols, odd)
-                d_dev = gpu.input(dev, stride, in_offset)
-                d_noise = gpu.input(noise, offset=in_offset)
-                d_flags = gpu.output((rows, cols), np.uint8, stride, out_offset)
-                gpu.call("ksp_threshold_simple", d_dev.ptr, d_noise.ptr, d_flags.ptr, rows, cols,
-                         stride, n_sigma, flag_value, int(transposed))  # fmt: skip
-                assert_equal(want, d_flags.read("flags, " + what), what)
-                d_dev.read("deviations, " + what)
-                d_noise.read("noise, " + what)
+                run_threshold_simple(gpu, dev, noise, want, transposed, row_stride(cols, odd),
+                                     in_offset, out_offset, what)  # fmt: skip
     assert 0.4 < flagged / total < 0.6
+
+
+SIMPLE_N_SIGMA, SIMPLE_FLAG_VALUE = 11.0, 4
+
+
+def simple_case(rs, oracle, rows, cols, transposed):
+    """(deviations, noise, the oracle's flags), the two arrays as the launcher takes them:
+    [rows][cols], which is [B][C] if `transposed`."""
+    n_sigma, flag_value = SIMPLE_N_SIGMA, SIMPLE_FLAG_VALUE
+    channels, baselines = (cols, rows) if transposed else (rows, cols)
+    noise = rs.uniform(5.0, 15.0, baselines).astype(F32)
+    limit = np.broadcast_to(F32(n_sigma) * noise, (channels, baselines))  # float32 product
+    # about half above the limit; some exactly on it (not flagged: the comparison is a
+    # strict >) and some one float32 above it
+    dev = (limit * rs.uniform(0.0, 2.0, limit.shape)).astype(F32)
+    pick = rs.random_sample(limit.shape)
+    exact, above = pick < 0.15, (pick >= 0.15) & (pick < 0.3)
+    dev[exact] = limit[exact]
+    dev[above] = np.nextafter(limit[above], F32(np.inf))
+    want = oracle.ThresholdSimpleHost(n_sigma, flag_value)(dev, noise)
+    assert not want[exact].any() and np.all(want[above] == flag_value)
+    if transposed:
+        dev, want = np.ascontiguousarray(dev.T), np.ascontiguousarray(want.T)
+    return dev, noise, want
+
+
+def shared(gpu, like, dev):
+    """The stride that deviations (float32) and flags (uint8) of one shape share."""
+    return gpu.shared_stride(like, [("deviations",) + dev.shape + (F32,),
+                                    ("flags",) + dev.shape + (np.uint8,)])  # fmt: skip
+
+
+def run_threshold_simple(gpu, dev, noise, want, transposed, stride, in_offset, out_offset, what):
+    rows, cols = dev.shape
+    stride = shared(gpu, stride, dev)
+    d_dev = gpu.input(dev, stride, in_offset, role="deviations")
+    d_noise = gpu.input(noise, offset=in_offset)
+    d_flags = gpu.output((rows, cols), np.uint8, stride, out_offset, role="flags")
+    gpu.call("ksp_threshold_simple", d_dev.ptr, d_noise.ptr, d_flags.ptr, rows, cols,
+             stride, SIMPLE_N_SIGMA, SIMPLE_FLAG_VALUE, int(transposed))  # fmt: skip
+    assert_equal(want, d_flags.read("flags, " + what), what)
+    d_dev.read("deviations, " + what)
+    d_noise.read("noise, " + what)
 
 
 # ------------------------------------------------------------------------- threshold_sum
@@ -333,20 +376,27 @@ def test_threshold_sum(channel_major, gpu, sum_cases):
             dev, want = np.ascontiguousarray(dev.T), np.ascontiguousarray(want.T)
         for name, odd, in_offset, out_offset in cases("ABCD"):
             what = f"{channels} x {baselines}, channel-major {channel_major}, case {name}"
-            stride = row_stride(dev.shape[1], odd)
-            d_dev = gpu.input(dev, stride, in_offset)
-            d_noise = gpu.input(noise, offset=in_offset)
-            d_flags = gpu.output(dev.shape, np.uint8, stride, out_offset)
-            if channel_major:
-                gpu.call("ksp_threshold_sum_cm", d_dev.ptr, d_noise.ptr, d_flags.ptr, channels,
-                         baselines, stride, 11.0, SUM_SCALES, 4, 1)  # fmt: skip
-            else:
-                gpu.call("ksp_threshold_sum", d_dev.ptr, d_noise.ptr, d_flags.ptr, channels,
-                         baselines, stride, 11.0, SUM_SCALES, 4, 1, 0)  # fmt: skip
-            assert_equal(want, d_flags.read("flags, " + what), what)
-            d_dev.read("deviations, " + what)
-            d_noise.read("noise, " + what)
+            run_threshold_sum(gpu, dev, noise, want, channel_major, row_stride(dev.shape[1], odd),
+                              in_offset, out_offset, what)  # fmt: skip
     assert flagged > 0
+
+
+def run_threshold_sum(gpu, dev, noise, want, channel_major, stride, in_offset, out_offset, what):
+    """`dev` and `want` as the launcher takes them: [C][B] if `channel_major`, else [B][C]."""
+    channels, baselines = dev.shape if channel_major else dev.shape[::-1]
+    stride = shared(gpu, stride, dev)
+    d_dev = gpu.input(dev, stride, in_offset, role="deviations")
+    d_noise = gpu.input(noise, offset=in_offset)
+    d_flags = gpu.output(dev.shape, np.uint8, stride, out_offset, role="flags")
+    if channel_major:
+        gpu.call("ksp_threshold_sum_cm", d_dev.ptr, d_noise.ptr, d_flags.ptr, channels,
+                 baselines, stride, 11.0, SUM_SCALES, 4, 1)  # fmt: skip
+    else:
+        gpu.call("ksp_threshold_sum", d_dev.ptr, d_noise.ptr, d_flags.ptr, channels,
+                 baselines, stride, 11.0, SUM_SCALES, 4, 1, 0)  # fmt: skip
+    assert_equal(want, d_flags.read("flags, " + what), what)
+    d_dev.read("deviations, " + what)
+    d_noise.read("noise, " + what)
 
 
 # ---------------------------------------------------------------------------- background
@@ -366,7 +416,6 @@ def background_inputs(oracle):
 @pytest.mark.parametrize("width", [3, 13, 33])  # 33: the wide-window kernel
 def test_background(width, mode, gpu, oracle, background_inputs):
     """in and out share `stride`; per-sample flags have a stride of their own."""
-    mode_value = {"NONE": 0, "CHANNEL": 1, "FULL": 2}[mode]
     for is_amplitude in (True, False):
         for channels in (40, 700):
             for baselines in (1, 63, 65, 130):
@@ -377,22 +426,30 @@ def test_background(width, mode, gpu, oracle, background_inputs):
                 for name, odd, in_offset, _ in cases("ABC"):
                     what = (f"{channels} x {baselines}, width {width}, {mode}, amplitude "
                             f"{is_amplitude}, case {name}")  # fmt: skip
-                    stride = row_stride(baselines, odd)
-                    src = gpu.input(data, stride, in_offset)
-                    out = gpu.output((channels, baselines), F32, stride)
-                    d_flags, flags_stride = None, 0
-                    if mode == "CHANNEL":
-                        d_flags = gpu.input(flags, offset=in_offset)
-                    elif mode == "FULL":
-                        flags_stride = row_stride(baselines, odd, 1)
-                        d_flags = gpu.input(flags, flags_stride, in_offset)
-                    gpu.call("ksp_background_median_filter", src.ptr, out.ptr,
-                             None if d_flags is None else d_flags.ptr, channels, baselines, stride,
-                             flags_stride, width, int(is_amplitude), mode_value, 0)  # fmt: skip
-                    assert_equal(want, out.read("out, " + what), what)
-                    src.read("in, " + what)
-                    if d_flags is not None:
-                        d_flags.read("flags, " + what)
+                    run_background(gpu, data, flags, want, width, mode, odd, in_offset, what)
+
+
+def run_background(gpu, data, flags, want, width, mode, odd, in_offset, what):
+    channels, baselines = data.shape
+    is_amplitude = data.dtype == F32
+    stride = gpu.shared_stride(row_stride(baselines, odd), [("in",) + data.shape + (data.dtype,),
+                                                            ("out",) + data.shape + (F32,)])  # fmt: skip
+    src = gpu.input(data, stride, in_offset, role="in")
+    out = gpu.output((channels, baselines), F32, stride, role="out")
+    d_flags, flags_stride = None, 0
+    if mode == "CHANNEL":
+        d_flags = gpu.input(flags, offset=in_offset)
+    elif mode == "FULL":
+        d_flags = gpu.input(flags, row_stride(baselines, odd, 1), in_offset, role="flags")
+        flags_stride = d_flags.stride
+    gpu.call("ksp_background_median_filter", src.ptr, out.ptr,
+             None if d_flags is None else d_flags.ptr, channels, baselines, stride,
+             flags_stride, width, int(is_amplitude), {"NONE": 0, "CHANNEL": 1, "FULL": 2}[mode],
+             0)  # fmt: skip
+    assert_equal(want, out.read("out, " + what), what)
+    src.read("in, " + what)
+    if d_flags is not None:
+        d_flags.read("flags, " + what)
 
 
 # ----------------------------------------------------------------------------- maskedsum
@@ -408,15 +465,21 @@ def test_maskedsum(use_amplitudes, gpu, oracle):
         scale = np.sum(np.abs(data) * mask[:, None], axis=0)  # cancellation-safe tolerance
         for name, odd, in_offset, _ in cases("ABC"):
             what = f"{rows} x {cols}, amplitudes {use_amplitudes}, case {name}"
-            src = gpu.input(data, row_stride(cols, odd), in_offset)
-            d_mask = gpu.input(mask, offset=in_offset)
-            out = gpu.output(cols, F32 if use_amplitudes else np.complex64, offset=int(name != "A"))
-            gpu.call("ksp_maskedsum_float", src.ptr, d_mask.ptr, out.ptr, src.stride, rows, cols,
-                     int(use_amplitudes))  # fmt: skip
-            got = out.read("out, " + what)[0]
-            np.testing.assert_array_less(np.abs(got - want), 1e-6 * scale + 1e-30, err_msg=what)
-            src.read("in, " + what)
-            d_mask.read("mask, " + what)
+            run_maskedsum(gpu, data, mask, want, scale, use_amplitudes, row_stride(cols, odd),
+                          in_offset, int(name != "A"), what)  # fmt: skip
+
+
+def run_maskedsum(gpu, data, mask, want, scale, use_amplitudes, stride, in_offset, out_offset, what):
+    rows, cols = data.shape
+    src = gpu.input(data, stride, in_offset, role="in")
+    d_mask = gpu.input(mask, offset=in_offset)
+    out = gpu.output(cols, F32 if use_amplitudes else np.complex64, offset=out_offset)
+    gpu.call("ksp_maskedsum_float", src.ptr, d_mask.ptr, out.ptr, src.stride, rows, cols,
+             int(use_amplitudes))  # fmt: skip
+    got = out.read("out, " + what)[0]
+    np.testing.assert_array_less(np.abs(got - want), 1e-6 * scale + 1e-30, err_msg=what)
+    src.read("in, " + what)
+    d_mask.read("mask, " + what)
 
 
 # ------------------------------------------------------------------------- fused flagger
@@ -441,45 +504,56 @@ def test_flagger_fused(channels, baselines, width, keep_deviations, ring, path, 
     """`vis` is 16-byte aligned with an even stride, as the ABI requires; every other array is
     a sub-view. `flags` in particular is a column block of a wider array: the zero fill ahead
     of the kernel may clear its rows and nothing between them."""
-    from katsdpsigproc_amd import accel
+    vis, masks = fused_inputs(channels, baselines, width)
+    for mode in ("NONE", "CHANNEL", "FULL"):
+        if ring and mode != "NONE":
+            continue  # the ring kernel takes no input flags
+        run_flagger_fused(gpu, oracle, vis, masks[mode], mode, width, keep_deviations, ring, path)
 
+
+def fused_inputs(channels, baselines, width):
+    """(vis, input flags per mode) for a shape of FUSED_SHAPES."""
     vis = inputs.add_rfi(inputs.generate_data(channels, baselines, seed=width), seed=baselines)
     rs = np.random.RandomState(channels)
     masks = {"NONE": None, "CHANNEL": inputs.channel_mask(channels, seed=3) * np.uint8(2),
              "FULL": (rs.random_sample(vis.shape) < 1.0 / 16.0).astype(np.uint8) * np.uint8(2)}  # fmt: skip
-    for mode, mode_value in (("NONE", 0), ("CHANNEL", 1), ("FULL", 2)):
-        if ring and mode != "NONE":
-            continue  # the ring kernel takes no input flags
-        what = f"{channels} x {baselines}, width {width}, {mode}"
-        mask = masks[mode]
-        want_flags, want_noise, want_dev = oracle.flagger_full(
-            vis, mask, width=width, n_sigma=11.0, want_deviations=True)
-        assert want_flags.any(), what
-        d_vis = gpu.input(vis, baselines + 2)
-        assert d_vis.address % 16 == 0 and d_vis.stride % 2 == 0
-        d_mask, mask_stride = None, 0
-        if mode == "CHANNEL":
-            d_mask = gpu.input(mask, offset=1)
-        elif mode == "FULL":
-            mask_stride = baselines + 7
-            d_mask = gpu.input(mask, mask_stride, offset=1)
-        d_flags = gpu.output(vis.shape, np.uint8, baselines + 5)
-        d_noise = gpu.output(baselines, F32, offset=1)
-        d_dev = gpu.output(vis.shape, F32, baselines + 3) if keep_deviations else None
-        workspace = accel.DeviceArray(gpu.context, (16,), np.uint32)  # 64 bytes, zeroed once
-        workspace.zero(gpu.queue)
-        with _lib.fused_ring_mode(ring):
-            gpu.call("ksp_flagger_fused", d_vis.ptr, None if d_mask is None else d_mask.ptr,
-                     d_flags.ptr, None if d_dev is None else d_dev.ptr, d_noise.ptr, channels,
-                     baselines, d_vis.stride, mask_stride, d_flags.stride,
-                     0 if d_dev is None else d_dev.stride, width, 0, mode_value, 1, 11.0,
-                     FUSED_SCALES, 4, 1, ctypes.c_void_p(workspace.buffer.ptr))  # fmt: skip
-            assert _lib.call("ksp_flagger_fused_last_path") == path, what
-        assert_equal(want_flags, d_flags.read("flags, " + what), what)
-        assert_equal(want_noise.astype(F32)[np.newaxis], d_noise.read("noise, " + what), what)
-        if d_dev is not None:
-            assert_equal(want_dev.astype(F32), d_dev.read("deviations, " + what), what)
-        d_vis.read("vis, " + what)
-        if d_mask is not None:
-            d_mask.read("in_flags, " + what)
-        assert not workspace.get(gpu.queue).any(), "the workspace was not left zeroed: " + what
+    return vis, masks
+
+
+def run_flagger_fused(gpu, oracle, vis, mask, mode, width, keep_deviations, ring, path):
+    from katsdpsigproc_amd import accel
+
+    channels, baselines = vis.shape
+    what = f"{channels} x {baselines}, width {width}, {mode}"
+    want_flags, want_noise, want_dev = oracle.flagger_full(
+        vis, mask, width=width, n_sigma=11.0, want_deviations=True)
+    assert want_flags.any(), what
+    d_vis = gpu.input(vis, baselines + 2, role="vis")
+    assert d_vis.address % 16 == 0 and d_vis.stride % 2 == 0
+    d_mask, mask_stride = None, 0
+    if mode == "CHANNEL":
+        d_mask = gpu.input(mask, offset=1)
+    elif mode == "FULL":
+        d_mask = gpu.input(mask, baselines + 7, offset=1, role="in_flags")
+        mask_stride = d_mask.stride
+    d_flags = gpu.output(vis.shape, np.uint8, baselines + 5, role="flags")
+    d_noise = gpu.output(baselines, F32, offset=1)
+    d_dev = gpu.output(vis.shape, F32, baselines + 3, role="deviations") if keep_deviations else None
+    workspace = accel.DeviceArray(gpu.context, (16,), np.uint32)  # 64 bytes, zeroed once
+    workspace.zero(gpu.queue)
+    with _lib.fused_ring_mode(ring):
+        gpu.call("ksp_flagger_fused", d_vis.ptr, None if d_mask is None else d_mask.ptr,
+                 d_flags.ptr, None if d_dev is None else d_dev.ptr, d_noise.ptr, channels,
+                 baselines, d_vis.stride, mask_stride, d_flags.stride,
+                 0 if d_dev is None else d_dev.stride, width, 0,
+                 {"NONE": 0, "CHANNEL": 1, "FULL": 2}[mode], 1, 11.0,
+                 FUSED_SCALES, 4, 1, ctypes.c_void_p(workspace.buffer.ptr))  # fmt: skip
+        assert _lib.call("ksp_flagger_fused_last_path") == path, what
+    assert_equal(want_flags, d_flags.read("flags, " + what), what)
+    assert_equal(want_noise.astype(F32)[np.newaxis], d_noise.read("noise, " + what), what)
+    if d_dev is not None:
+        assert_equal(want_dev.astype(F32), d_dev.read("deviations, " + what), what)
+    d_vis.read("vis, " + what)
+    if d_mask is not None:
+        d_mask.read("in_flags, " + what)
+    assert not workspace.get(gpu.queue).any(), "the workspace was not left zeroed: " + what
