@@ -702,6 +702,50 @@ int ksp_fit_delays(int device, void *stream, const void *gains, const uint8_t *s
                    int n_fft, int refine, int status_mask, int corrections,
                    double channel_width);
 
+/* interpolate_gains: per input, the gains that ksp_solve_gains leaves, filled across the
+ * channels it left without a value, as a table that ksp_apply_gains can apply to another scan,
+ * in one launch (no reference counterpart; bit for bit what rfi/host.py InterpolateGainsHost
+ * computes; every step is one float32 operation, rounded once, a multiply then an add, never an
+ * fma, real and imaginary parts apart, division and square root correctly rounded; a complex
+ * product a b is (a.re b.re - a.im b.im, a.re b.im + a.im b.re)).
+ * gains, model, out: complex64 [channels][stride], of which n_inputs per row are data; status:
+ * uint8 [channels] or NULL; model: what ksp_fit_delays writes with corrections 0 (taken as unit
+ * modulus), or NULL; scale: complex64 [n_inputs] or NULL; kept, filled: int32 [n_inputs];
+ * fill_status: uint8 [n_inputs]; mean_amplitude: float32 [n_inputs], or NULL for no
+ * normalisation. Per input p, with g = gains[c][p] and m = model[c][p]:
+ *   1. c is kept if both parts of g are finite, (status is NULL or status[c] & status_mask == 0)
+ *      and (model is NULL or both parts of m are finite), else missing; kept[p] counts the kept
+ *      ones; none: bit 0 of fill_status[p].
+ *   2. d = (g.re m.re + g.im m.im, g.im m.re - g.re m.im), or g without model.
+ *   3. for a kept c, s[c] = the sum of d over the kept channels of [c - smooth / 2,
+ *      c + smooth / 2] inside the band, added in ascending order from +0, divided by float of
+ *      their number; smooth == 1: s = d, no sum and no division.
+ *   4. with mean_amplitude: a = (the sum of sqrt(s.re s.re + s.im s.im) over the kept channels
+ *      as the halving tree over Cpad terms, the next power of two at or above channels, other
+ *      terms +0: n = Cpad; while n > 1: n /= 2, t[i] = t[i] + t[i + n] for i < n)
+ *      / float(kept[p]); mean_amplitude[p] = a, NaN if no channel is kept; a in (0, inf):
+ *      s = (s.re / a, s.im / a), else bit 0.
+ *   5. y[c] = s[c] for a kept c. For a missing c, with l the nearest kept channel below and r
+ *      the nearest above: both and r - l - 1 <= max_gap: t = float(c - l) / float(r - l),
+ *      y = s[l] + (s[r] - s[l]) t per part; only l and c - l <= max_gap: y = s[l]; only r and
+ *      r - c <= max_gap: y = s[r]; otherwise y = NaN and bit 1 of fill_status[p]. filled[p]
+ *      counts the missing channels that got a value.
+ *   6. with model, y = y m at every channel;  7. with scale, y = y scale[p];
+ *   8. corrections 1: q = y.re y.re + y.im y.im, out = q > 0 ? (y.re / q, -y.im / q) : NaN.
+ *   An input with bit 0 has NaN in its column of out, filled[p] = 0 and no other bit.
+ * channels is 1..16384, n_inputs at least 1, max_gap 0..16384, smooth odd and 1..31,
+ * status_mask 0..255, corrections 0 or 1. out may be gains itself (same pointer and stride) but
+ * must not overlap it otherwise, and shares no byte with model. Elements between n_inputs and a
+ * stride are neither read nor written. One kernel launch, one workgroup per input with
+ * 8 channels bytes of LDS, no workspace, no atomics. Every argument is checked before any
+ * device call. */
+int ksp_interpolate_gains(int device, void *stream, const void *gains, const uint8_t *status,
+                          const void *model, const void *scale, void *out, int *kept,
+                          int *filled, uint8_t *fill_status, float *mean_amplitude,
+                          int channels, int n_inputs, int gains_stride, int model_stride,
+                          int out_stride, int max_gap, int smooth, int status_mask,
+                          int corrections);
+
 /* range_percentiles: per channel and per range of baselines, the [0, 100, 25, 75, 50] %
  * amplitudes ("lower" element) of the samples that are neither NaN nor flagged under a mask,
  * how many those are, and the OR of the range's flags, all ranges in one launch (no reference

@@ -1416,6 +1416,209 @@ class FitDelaysHost:
         return delays, phasors, amplitudes, fit_status, model
 
 
+class InterpolateGainsHost:
+    """The gains that :class:`SolveGainsHost` solves on a calibrator, made into a table that
+    :class:`ApplyGainsHost` can apply to a target: per input, the channels the solver left
+    without a value (NaN, or excluded by `status`) are filled from their neighbours across gaps
+    of at most `max_gap` channels, after the delay that :class:`FitDelaysHost` fitted is divided
+    out (linear interpolation of a wound phase loses amplitude) and before it is multiplied
+    back in; optionally the bandpass is smoothed, normalised to a mean amplitude of 1,
+    multiplied by the band-wide gain of a later solve, and inverted. No reference counterpart;
+    this class is the definition that the device operation
+    (:class:`.ingest.InterpolateGainsTemplate`) matches bit for bit.
+
+    Every float step is one float32 operation, rounded once (a multiply, then an add, never an
+    fma; real and imaginary parts apart; correctly rounded division and square root), as in
+    :class:`SolveGainsHost`. A complex product ``a*b`` is ``(a.re*b.re - a.im*b.im, a.re*b.im +
+    a.im*b.re)``. Per input ``p``, with ``g = gains[c, p]`` and ``m = model[c, p]``:
+
+    1. *Kept channels.* ``c`` is kept if both parts of ``g`` are finite, `status` is absent or
+       ``status[c] & status_mask == 0``, and `model` is absent or both parts of ``m`` are
+       finite; every other channel is *missing*. ``kept[p]`` counts the kept ones. If there is
+       none, bit 0 of ``fill_status[p]`` (:attr:`NO_DATA`) is set.
+    2. *De-rotate.* ``d = g*conj(m) = (g.re*m.re + g.im*m.im, g.im*m.re - g.re*m.im)``, or
+       ``d = g`` without `model`.
+    3. *Smooth.* For a kept ``c``, ``s[c]`` is the sum of ``d`` over the kept channels of
+       ``[c - smooth//2, c + smooth//2]`` that lie inside the band, added one by one in
+       ascending channel order from +0, divided by float32 of their number (at least 1: ``c``
+       itself). With ``smooth=1`` there is no sum and no division: ``s = d`` bit for bit.
+    4. *Normalise* (with `normalise`). ``a`` is the sum of ``sqrt(s.re*s.re + s.im*s.im)`` over
+       the kept channels divided by float32 of ``kept[p]``, where the sum is the halving tree
+       of :class:`FitDelaysHost` over ``Cpad`` terms (the next power of two at or above
+       ``channels``; the terms of the other channels are +0): ``n = Cpad; while n > 1: n //= 2;
+       t[:n] = t[:n] + t[n:2n]``. ``mean_amplitude[p] = a``, NaN if no channel is kept. If ``a``
+       is in ``(0, inf)``, ``s = (s.re/a, s.im/a)``; otherwise bit 0 is set.
+    5. *Fill.* ``y[c] = s[c]`` for a kept ``c``. For a missing ``c`` let ``l`` be the nearest
+       kept channel below it and ``r`` the nearest above it. If both exist and ``r - l - 1 <=
+       max_gap`` (the gap, whole, is at most `max_gap` channels long), ``t = float32(c - l) /
+       float32(r - l)`` and ``y = s[l] + (s[r] - s[l])*t`` per part. If only one exists (``c``
+       lies beyond the first or the last kept channel) and ``c`` is at most `max_gap` channels
+       away from it, ``y`` is its ``s``: the ends of the band hold the nearest value, channel by
+       channel. Otherwise ``y`` is NaN and bit 1 (:attr:`GAP_LEFT`) is set. ``filled[p]``
+       counts the missing channels that got a value (whatever IEEE made of it).
+    6. *Re-rotate.* With `model`, ``y = y*m`` at every channel, kept or not; a model that is not
+       finite gives what IEEE gives. `model` is taken to have unit modulus: its rounding enters
+       the amplitude twice, once in each rotation, up to ``2**-22`` relative, which is accepted.
+    7. *Scale.* With `scale`, ``y = y*scale[p]``.
+    8. *Corrections.* With `corrections` the output is ``(y.re/q, -y.im/q)`` where ``q =
+       y.re*y.re + y.im*y.im > 0``, else NaN: what :class:`ApplyGainsHost` multiplies by.
+
+    An input with bit 0 set has NaN in its whole column of ``out``, ``filled[p] = 0`` and no
+    other bit. Consequence: with ``smooth=1`` and without `model`, `scale`, `normalise` and
+    `corrections`, ``out`` equals ``gains`` bit for bit on every kept channel.
+
+    Parameters
+    ----------
+    max_gap
+        Longest gap that is filled, in channels, 0..16384; 0 fills nothing
+    smooth
+        Width of the running mean in channels, odd, 1..31
+    normalise
+        ``True``: divide each input's column by its mean amplitude
+    status_mask
+        Bits of `status` that make a channel missing, 0..255 (:func:`check_mask_byte`)
+    corrections
+        ``True``: return the reciprocal gains
+    """
+
+    MAX_CHANNELS = 16384
+    MAX_GAP = 16384
+    MAX_SMOOTH = 31
+    NO_DATA, GAP_LEFT = 1, 2
+
+    def __init__(self, max_gap: int, smooth: int = 1, normalise: bool = False,
+                 status_mask: int = 0xFF, corrections: bool = False) -> None:  # fmt: skip
+        for name, value in (("max_gap", max_gap), ("smooth", smooth)):
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+                raise TypeError(f"{name} {value!r} is not an integer")
+        if not 0 <= max_gap <= self.MAX_GAP:
+            raise ValueError(f"max_gap must be 0..{self.MAX_GAP}")
+        if not 1 <= smooth <= self.MAX_SMOOTH or smooth % 2 == 0:
+            raise ValueError(f"smooth must be odd and 1..{self.MAX_SMOOTH}")
+        self.max_gap = int(max_gap)
+        self.smooth = int(smooth)
+        self.normalise = bool(normalise)
+        self.status_mask = check_mask_byte("status_mask", status_mask)
+        self.corrections = bool(corrections)
+
+    @classmethod
+    def check_shape(cls, channels: int, n_inputs: int) -> None:
+        """``ValueError`` if `channels` is outside 1..16384 or `n_inputs` below 1."""
+        if not 1 <= channels <= cls.MAX_CHANNELS:
+            raise ValueError(f"channels must be 1..{cls.MAX_CHANNELS}")
+        if n_inputs < 1:
+            raise ValueError("n_inputs must be at least 1")
+
+    @staticmethod
+    def _product(a_re, a_im, b_re, b_im):
+        return a_re * b_re - a_im * b_im, a_re * b_im + a_im * b_re
+
+    def __call__(self, gains: np.ndarray, status: Optional[np.ndarray] = None,
+                 model: Optional[np.ndarray] = None, scale: Optional[np.ndarray] = None):  # fmt: skip
+        """``(out, kept, filled, fill_status, mean_amplitude)``: complex64 (channels, n_inputs),
+        int32, int32 and uint8 (n_inputs,), and float32 (n_inputs,) with `normalise`, else
+        ``None``; for complex64 `gains` (channels, n_inputs), optional uint8 `status`
+        (channels,), optional complex64 `model` (channels, n_inputs) and optional complex64
+        `scale` (n_inputs,). ``ValueError``, naming the argument, for a wrong dtype, rank or
+        shape (channels 1..16384, n_inputs at least 1). No argument is modified."""
+        gains = _check_array("gains", gains, np.complex64, "(channels, n_inputs)",
+                             lambda s: len(s) == 2 and 1 <= s[0] <= self.MAX_CHANNELS
+                             and s[1] >= 1)  # fmt: skip
+        channels, n_inputs = gains.shape
+        if status is not None:
+            status = _check_array("status", status, np.uint8, "(channels,)",
+                                  lambda s: s == (channels,))  # fmt: skip
+        if model is not None:
+            model = _check_array("model", model, np.complex64, "(channels, n_inputs)",
+                                 lambda s: s == gains.shape)  # fmt: skip
+        if scale is not None:
+            scale = _check_array("scale", scale, np.complex64, "(n_inputs,)",
+                                 lambda s: s == (n_inputs,))  # fmt: skip
+        f32 = np.float32
+        nan, one = f32(np.nan), f32(1)
+        kept = np.isfinite(gains.real) & np.isfinite(gains.imag)
+        if status is not None:
+            kept &= ((status & np.uint8(self.status_mask)) == 0)[:, np.newaxis]
+        if model is not None:
+            kept &= np.isfinite(model.real) & np.isfinite(model.imag)
+        n_kept = kept.sum(axis=0).astype(np.int32)
+        failed = n_kept == 0
+        mean_amplitude = None
+        with np.errstate(all="ignore"):
+            s_re, s_im = gains.real, gains.imag
+            if model is not None:
+                m_re, m_im = model.real, model.imag
+                s_re, s_im = s_re * m_re + s_im * m_im, s_im * m_re - s_re * m_im
+            if self.smooth > 1:
+                reach = self.smooth // 2
+                sum_re = np.zeros(gains.shape, f32)
+                sum_im = np.zeros(gains.shape, f32)
+                count = np.zeros(gains.shape, np.int32)
+                for offset in range(-reach, reach + 1):  # channel c + offset, ascending
+                    lo, hi = max(0, -offset), min(channels, channels - offset)
+                    if lo >= hi:
+                        continue
+                    to, of = slice(lo, hi), slice(lo + offset, hi + offset)
+                    sum_re[to] = np.where(kept[of], sum_re[to] + s_re[of], sum_re[to])
+                    sum_im[to] = np.where(kept[of], sum_im[to] + s_im[of], sum_im[to])
+                    count[to] += kept[of]
+                number = np.maximum(count, 1).astype(f32)  # (only kept channels are used)
+                s_re, s_im = sum_re / number, sum_im / number
+            if self.normalise:
+                c_pad = 1
+                while c_pad < channels:
+                    c_pad *= 2
+                terms = np.zeros((c_pad, n_inputs), f32)
+                terms[:channels] = np.where(kept, np.sqrt(s_re * s_re + s_im * s_im), f32(0))
+                total = FitDelaysHost._tree_sum(terms)
+                mean_amplitude = np.where(failed, nan, total / np.maximum(n_kept, 1).astype(f32))
+                usable = (mean_amplitude > 0) & (mean_amplitude < np.inf)
+                safe = np.where(usable, mean_amplitude, one)
+                s_re, s_im = s_re / safe, s_im / safe
+                failed = failed | ~usable
+                assert mean_amplitude.dtype == f32
+            # the nearest kept channel at or below and at or above every channel
+            index = np.arange(channels, dtype=np.int64)[:, np.newaxis]
+            none_above = np.int64(channels)
+            below = np.maximum.accumulate(np.where(kept, index, -1), axis=0)
+            above = np.minimum.accumulate(np.where(kept, index, none_above)[::-1], axis=0)[::-1]
+            has_l, has_r = below >= 0, above < none_above
+            l, r = np.maximum(below, 0), np.minimum(above, channels - 1)
+            sl_re, sl_im = np.take_along_axis(s_re, l, 0), np.take_along_axis(s_im, l, 0)
+            sr_re, sr_im = np.take_along_axis(s_re, r, 0), np.take_along_axis(s_im, r, 0)
+            span = np.where(has_l & has_r & ~kept, r - l, 1)
+            t = (index - l).astype(f32) / span.astype(f32)
+            between = has_l & has_r & (above - below - 1 <= self.max_gap)
+            held_l = has_l & ~has_r & (index - below <= self.max_gap)
+            held_r = has_r & ~has_l & (above - index <= self.max_gap)
+            y_re = np.where(between, sl_re + (sr_re - sl_re) * t,
+                            np.where(held_l, sl_re, np.where(held_r, sr_re, nan)))  # fmt: skip
+            y_im = np.where(between, sl_im + (sr_im - sl_im) * t,
+                            np.where(held_l, sl_im, np.where(held_r, sr_im, nan)))  # fmt: skip
+            y_re, y_im = np.where(kept, s_re, y_re), np.where(kept, s_im, y_im)
+            got = ~kept & (between | held_l | held_r)
+            if model is not None:
+                y_re, y_im = self._product(y_re, y_im, m_re, m_im)
+            if scale is not None:
+                y_re, y_im = self._product(y_re, y_im, scale.real[np.newaxis, :],
+                                           scale.imag[np.newaxis, :])  # fmt: skip
+            if self.corrections:
+                q = y_re * y_re + y_im * y_im
+                pos = q > 0
+                safe = np.where(pos, q, one)  # (no 0 / 0 where the quotient is not used)
+                y_re = np.where(pos, y_re / safe, nan)
+                y_im = np.where(pos, -y_im / safe, nan)
+            assert y_re.dtype == f32 and y_im.dtype == f32
+        out = np.empty(gains.shape, np.complex64)
+        out.real[...] = np.where(failed, nan, y_re)
+        out.imag[...] = np.where(failed, nan, y_im)
+        filled = np.where(failed, 0, got.sum(axis=0)).astype(np.int32)
+        fill_status = np.where(failed, self.NO_DATA,
+                               np.where((~kept & ~got).any(axis=0), self.GAP_LEFT, 0)
+                               ).astype(np.uint8)  # fmt: skip
+        return out, n_kept, filled, fill_status, mean_amplitude
+
+
 def check_ranges(ranges, baselines: Optional[int] = None) -> Tuple[Tuple[int, int], ...]:
     """`ranges` as a tuple of 1 to :attr:`RangePercentilesHost.MAX_RANGES` pairs of ints
     ``(start, stop)`` with ``0 <= start <= stop``, ``stop - start`` at most

@@ -24,7 +24,11 @@ with float64 phases, and optionally the data divided by them, in one launch, bit
 :class:`.host.PredictHost` defines. And the step behind the solver: per input, the delay and
 phase fitted to the solved gains across the band and the smooth phasor that is applied in their
 place, in one launch with one workgroup per input, bit for bit what
-:class:`.host.FitDelaysHost` defines. The classes follow DESIGN.md, "Adding an operation".
+:class:`.host.FitDelaysHost` defines. And the step that makes a table for a target scan of
+both: per input, the solved gains with the delay divided out, smoothed, normalised, filled
+across the channels the solver lost, and recombined with the delay and a band-wide gain, in one
+launch with one workgroup per input, bit for bit what :class:`.host.InterpolateGainsHost`
+defines. The classes follow DESIGN.md, "Adding an operation".
 """
 
 import ctypes
@@ -979,6 +983,169 @@ class FitDelaysHostFromDevice:
         out = _native_op.run_once(fn, self.command_queue, {"gains": gains, "status": status},
                                   names)  # fmt: skip
         return tuple(out) + (() if template.model else (None,))
+
+
+class InterpolateGainsTemplate(_native_op.NativeTemplate):
+    """What stands between :class:`SolveGainsTemplate` / :class:`FitDelaysTemplate` and the
+    :class:`ApplyGainsTemplate` of a target scan: per input, the solved gains with the delay
+    model divided out, smoothed, normalised, filled across the channels the solver left without
+    a value (gaps of at most `max_gap` channels), multiplied by the delay model and by the
+    band-wide gain of a later solve again, and inverted; one kernel launch with one workgroup
+    per input; see :class:`host.InterpolateGainsHost` for every step.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    max_gap, smooth, normalise, status_mask, corrections
+        As for :class:`host.InterpolateGainsHost` (same errors)
+    status
+        ``True``: there is a `status` slot (:class:`SolveGains`'s)
+    model
+        ``True``: there is a `model` slot (:class:`FitDelays`'s, fitted with
+        ``corrections=False``)
+    scale
+        ``True``: there is a `scale` slot
+    tuning
+        The kernel picks its launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.InterpolateGainsHost
+    KERNEL = "ksp_interpolate_gains"
+
+    def __init__(self, context: AbstractContext, max_gap: int, smooth: int = 1,
+                 normalise: bool = False, status: bool = True, status_mask: int = 0xFF,
+                 model: bool = True, scale: bool = False, corrections: bool = False,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        self.checked = host.InterpolateGainsHost(max_gap, smooth, normalise, status_mask,
+                                                 corrections)  # fmt: skip
+        self.max_gap = self.checked.max_gap
+        self.smooth = self.checked.smooth
+        self.normalise = self.checked.normalise
+        self.status = bool(status)
+        self.status_mask = self.checked.status_mask
+        self.model = bool(model)
+        self.scale = bool(scale)
+        self.corrections = self.checked.corrections
+        self._setup(context, tuning)
+
+
+class InterpolateGains(_native_op.NativeOperation):
+    """Concrete :class:`InterpolateGainsTemplate` (``ValueError`` if `channels` is outside
+    1..16384 or `n_inputs` below 1).
+
+    .. rubric:: Slots
+
+    **gains** : channels x n_inputs, complex64
+    **status** : channels, uint8 (only with ``status``)
+    **model** : channels x n_inputs, complex64 (only with ``model``)
+    **scale** : n_inputs, complex64 (only with ``scale``)
+    **out** : channels x n_inputs, complex64
+    **kept** : n_inputs, int32
+    **filled** : n_inputs, int32
+    **fill_status** : n_inputs, uint8
+    **mean_amplitude** : n_inputs, float32 (only with ``normalise``)
+
+    Every padded dimension is an object of its own, so ``gains`` and ``status`` can be
+    compounded with :class:`SolveGains`'s outputs, ``model`` with :class:`FitDelays`'s and
+    ``out`` with :class:`ApplyGains`'s ``gains``, each taking the other's padding. ``out`` may
+    be bound to the buffer of ``gains``: the operation then works in place.
+    """
+
+    def __init__(self, template: InterpolateGainsTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, n_inputs: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, n_inputs, allocator)
+        template.checked.check_shape(channels, n_inputs)
+        self.n_inputs = n_inputs
+
+        def per_input(dtype) -> accel.IOSlot:
+            return accel.IOSlot((accel.Dimension(n_inputs),), dtype)
+
+        def per_channel() -> accel.IOSlot:
+            return accel.IOSlot((channels, accel.Dimension(n_inputs)), np.complex64)
+
+        self.slots["gains"] = per_channel()
+        if template.status:
+            self.slots["status"] = accel.IOSlot((accel.Dimension(channels),), np.uint8)
+        if template.model:
+            self.slots["model"] = per_channel()
+        if template.scale:
+            self.slots["scale"] = per_input(np.complex64)
+        self.slots["out"] = per_channel()
+        self.slots["kept"] = per_input(np.int32)
+        self.slots["filled"] = per_input(np.int32)
+        self.slots["fill_status"] = per_input(np.uint8)
+        if template.normalise:
+            self.slots["mean_amplitude"] = per_input(np.float32)
+
+    def _run(self) -> None:
+        template = self.template
+        gains = self.buffer("gains")
+        status = self.buffer("status") if template.status else None
+        model = self.buffer("model") if template.model else None
+        scale = self.buffer("scale") if template.scale else None
+        out = self.buffer("out")
+        mean_amplitude = self.buffer("mean_amplitude") if template.normalise else None
+        self._launch(
+            gains.buffer,
+            _native_op.pointer(status),
+            _native_op.pointer(model),
+            _native_op.pointer(scale),
+            out.buffer,
+            self.buffer("kept").buffer,
+            self.buffer("filled").buffer,
+            self.buffer("fill_status").buffer,
+            _native_op.pointer(mean_amplitude),
+            np.int32(self.channels),
+            np.int32(self.n_inputs),
+            np.int32(gains.padded_shape[1]),
+            _native_op.stride(model),
+            np.int32(out.padded_shape[1]),
+            np.int32(template.max_gap),
+            np.int32(template.smooth),
+            np.int32(template.status_mask),
+            np.int32(template.corrections),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        template = self.template
+        return {"max_gap": template.max_gap, "smooth": template.smooth,
+                "normalise": template.normalise, "status": template.status,
+                "status_mask": template.status_mask, "model": template.model,
+                "scale": template.scale, "corrections": template.corrections,
+                "channels": self.channels, "n_inputs": self.n_inputs}  # fmt: skip
+
+
+InterpolateGainsTemplate.operation_class = InterpolateGains
+
+
+class InterpolateGainsHostFromDevice:
+    """Make an :class:`InterpolateGainsTemplate` callable like
+    :class:`host.InterpolateGainsHost`: ``(gains, status=None, model=None, scale=None)`` in,
+    ``(out, kept, filled, fill_status, mean_amplitude or None)`` out; allocates on every call.
+    ``TypeError`` unless `status`, `model` and `scale` are given exactly when the template has
+    them."""
+
+    def __init__(self, template: InterpolateGainsTemplate,
+                 command_queue: AbstractCommandQueue) -> None:
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, gains: np.ndarray, status: Optional[np.ndarray] = None,
+                 model: Optional[np.ndarray] = None, scale: Optional[np.ndarray] = None):  # fmt: skip
+        template = self.template
+        _native_op.check_optional(status, template.status, "status")
+        _native_op.check_optional(model, template.model, "model")
+        _native_op.check_optional(scale, template.scale, "scale")
+        channels, n_inputs = np.shape(gains)
+        fn = template.instantiate(self.command_queue, channels, n_inputs)
+        names = ["out", "kept", "filled", "fill_status"] + (
+            ["mean_amplitude"] if template.normalise else [])  # fmt: skip
+        given = {"gains": gains, "status": status, "model": model, "scale": scale}
+        out = _native_op.run_once(fn, self.command_queue, given, names)
+        return tuple(out) + (() if template.normalise else (None,))
 
 
 class RangePercentilesTemplate(_native_op.NativeTemplate):
