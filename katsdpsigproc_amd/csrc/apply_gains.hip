@@ -22,15 +22,11 @@
 // depends on n_inputs alone), and every lane then picks its 32 gains per row with 8-byte LDS
 // reads. A sample costs 16 bytes of LDS reads.
 //
-// Geometry (ag_geometry, the only place that knows it). A workgroup of 256 threads owns a tile
-// of `tile_runs` runs (a power of two, 1 .. 256: the narrowest that holds a row, so a tile is at
-// most AG_TILE = 4096 baselines wide) and a chunk of `chunk` rows. Its threads are dealt to a
-// flat index over runs and rows: thread t owns run t % tile_runs of the tile and, of each stage,
-// the rows t / tile_runs, t / tile_runs + 256 / tile_runs, ..., so a narrow array still fills
-// its wavefronts. The chunk is a multiple of 256 / tile_runs chosen so that a launch has about
-// AG_TARGET_GROUPS workgroups where the array is large enough; a workgroup walks its chunk in
-// stages of at most ag_stage_rows rows, two barriers per stage. Workgroups are numbered in a
-// one-dimensional grid, and row bases are 64-bit.
+// Geometry (tile_grid.h). A workgroup of 256 threads owns a tile of `tile_runs` runs (1 .. 256,
+// so a tile is at most 4096 baselines wide) and a chunk of `chunk` rows, about AG_TARGET_GROUPS
+// workgroups to a launch: thread t owns run t % tile_runs of the tile and, of each stage, the
+// rows t / tile_runs, t / tile_runs + 256 / tile_runs, ... A workgroup walks its chunk in stages
+// of at most ag_stage_rows rows, two barriers per stage. Row bases are 64-bit.
 //
 // In place. A lane loads the vis, weights and flags of a run before it stores any of them, and
 // no other lane touches that run, so an output may be its input (same pointer, same stride). The
@@ -42,8 +38,10 @@
 // Traffic per sample: 8 + 4 + 1 bytes read and as many written, 26 in all (24, 18 and 16
 // without flags, weights or both); per lane 128 bytes of indices; per workgroup and stage the
 // rows of gains it stages, which come from L2 for all but the first workgroup to ask.
+#include "cal_math.h"
 #include "launch.h"
 #include "run16.h"
+#include "tile_grid.h"
 
 #define AG_THREADS 256
 #define AG_LDS_GAINS 4096       // gains a stage holds (8 bytes each)
@@ -62,30 +60,6 @@ static int ag_stage_rows(int n_inputs)
     return fit < AG_STAGE_ROWS_MAX ? fit : AG_STAGE_ROWS_MAX;
 }
 
-struct ag_geometry {
-    int tile_shift;  // log2(tile_runs)
-    int tiles;       // tiles per row
-    int chunk;       // rows per workgroup
-    long long groups;
-};
-
-static ag_geometry ag_make_geometry(int channels, int baselines)
-{
-    ag_geometry g;
-    const int runs_per_row = (int)(((long long)baselines + KSP_RUN - 1) / KSP_RUN);
-    g.tile_shift = 0;
-    while ((1 << g.tile_shift) < AG_THREADS && (1 << g.tile_shift) < runs_per_row) g.tile_shift++;
-    const int tile_runs = 1 << g.tile_shift;
-    g.tiles = (runs_per_row + tile_runs - 1) / tile_runs;
-    const int slots = AG_THREADS / tile_runs;  // rows a workgroup works on at once
-    long long chunk = (long long)channels * g.tiles / AG_TARGET_GROUPS / slots * slots;
-    if (chunk > channels) chunk = channels;  // (wide rows: the tiles alone are groups enough)
-    if (chunk < slots) chunk = slots;
-    g.chunk = (int)chunk;
-    g.groups = (channels + chunk - 1) / chunk * g.tiles;
-    return g;
-}
-
 template <bool HAS_W, bool HAS_F>
 __global__ __launch_bounds__(AG_THREADS) void apply_gains_kernel(
     const float2 *vis, const float *weights, const uint8_t *flags,
@@ -98,17 +72,11 @@ __global__ __launch_bounds__(AG_THREADS) void apply_gains_kernel(
     __shared__ float2 staged[AG_LDS_GAINS];
     const bool wide = aligned & AG_ALIGNED_DATA;
     const int tid = threadIdx.x;
-    const int tile = blockIdx.x % tiles;
-    const long long row_begin = (long long)(blockIdx.x / tiles) * chunk;
-    const long long row_end = min((long long)channels, row_begin + chunk);
-
-    const int tile_runs = 1 << tile_shift;
-    const int slot = tid >> tile_shift;
-    const int slots = AG_THREADS >> tile_shift;
-    // (64-bit: the columns of the lanes beyond the end of the last tile may pass 2^31)
-    const long long col0 = ((long long)tile * tile_runs + (tid & (tile_runs - 1))) * KSP_RUN;
-    // elements of the run inside the row: 0 for a lane beyond it, which then only helps to stage
-    const int valid = (int)min((long long)KSP_RUN, max(0ll, baselines - col0));
+    const ksp_tile_place at =
+        ksp_tile_locate(AG_THREADS, tiles, tile_shift, chunk, channels, baselines);
+    const long long row_begin = at.row_begin, row_end = at.row_end, col0 = at.col0;
+    const int slot = at.slot, slots = at.slots;
+    const int valid = at.valid;  // (0: the lane only helps to stage)
 
     // The lane's indices, once. Those outside 0 .. n_inputs - 1 are replaced by 0 and remembered.
     // (element by element as int32, which is all the alignment an unaligned `inputs` promises)
@@ -160,10 +128,12 @@ __global__ __launch_bounds__(AG_THREADS) void apply_gains_kernel(
 #pragma unroll
                 for (int i = 0; i < KSP_RUN; i++) {
                     const float2 ga = g[idx[i].x], gb = g[idx[i].y];
+                    // (ksp_cmul_conj(ga, gb) and ksp_cmul(v[i], c) written out: through the
+                    // helpers the compiler allots other registers, 92 .. 192 to 102 .. 163)
                     const float cr = __fadd_rn(__fmul_rn(ga.x, gb.x), __fmul_rn(ga.y, gb.y));
                     const float ci = __fsub_rn(__fmul_rn(ga.y, gb.x), __fmul_rn(ga.x, gb.y));
                     const bool ok = ((inr >> i) & 1u) && !__builtin_isnan(cr) && !__builtin_isnan(ci);
-                    const float p = __fadd_rn(__fmul_rn(cr, cr), __fmul_rn(ci, ci));
+                    const float p = ksp_norm2(make_float2(cr, ci));
                     const float re = __fsub_rn(__fmul_rn(v[i].x, cr), __fmul_rn(v[i].y, ci));
                     const float im = __fadd_rn(__fmul_rn(v[i].x, ci), __fmul_rn(v[i].y, cr));
                     v[i].x = ok ? re : v[i].x;
@@ -175,12 +145,7 @@ __global__ __launch_bounds__(AG_THREADS) void apply_gains_kernel(
                 if (HAS_W)
                     ksp_run_store(out_weights + row * out_weights_stride + col0, valid, wide, w);
                 if (HAS_F) {
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        // bit k of the nibble to bit 0 of byte k (no two products share a bit)
-                        const unsigned spread = (((bad >> (4 * q)) & 0xfu) * 0x00204081u) & 0x01010101u;
-                        f[q] |= spread * flag_value;
-                    }
+                    ksp_flag_spread(f, bad, flag_value);
                     ksp_run_store_bytes(out_flags + row * out_flags_stride + col0, valid, wide, f);
                 }
             }
@@ -204,10 +169,7 @@ extern "C" int ksp_apply_gains(int device, void *stream, const void *vis, const 
                               {"flags", flags, flags_stride, 1, true},
                               {"out_flags", out_flags, out_flags_stride, 1, true}};
     KSP_TRY(ksp_planes_given({in, table, {"inputs", inputs, 0, 4}, out}));
-    KSP_REQUIRE((weights == nullptr) == (out_weights == nullptr),
-                "weights and out_weights must both be NULL or both be given");
-    KSP_REQUIRE((flags == nullptr) == (out_flags == nullptr),
-                "flags and out_flags must both be NULL or both be given");
+    KSP_TRY(ksp_pairs_given_together(pairs));
     KSP_REQUIRE(channels >= 1, "channels must be at least 1");
     KSP_REQUIRE(baselines >= 1, "baselines must be at least 1");
     KSP_REQUIRE(n_inputs >= 1 && n_inputs <= AG_MAX_INPUTS, "n_inputs must be 1..4096");
@@ -215,17 +177,10 @@ extern "C" int ksp_apply_gains(int device, void *stream, const void *vis, const 
     KSP_TRY(ksp_planes_hold({in, out}, baselines, "baselines"));
     KSP_TRY(ksp_planes_hold({table}, n_inputs, "n_inputs"));
     KSP_TRY(ksp_planes_hold(pairs, baselines, "baselines"));
-    KSP_REQUIRE(
-        ksp_same_or_apart(vis, vis_stride, out_vis, out_vis_stride, channels, baselines, 8),
-        "out_vis overlaps vis without being vis with the same stride");
-    KSP_REQUIRE(weights == nullptr ||
-                    ksp_same_or_apart(weights, weights_stride, out_weights, out_weights_stride,
-                                      channels, baselines, 4),
-                "out_weights overlaps weights without being weights with the same stride");
-    KSP_REQUIRE(flags == nullptr || ksp_same_or_apart(flags, flags_stride, out_flags,
-                                                      out_flags_stride, channels, baselines, 1),
-                "out_flags overlaps flags without being flags with the same stride");
-    const ag_geometry geom = ag_make_geometry(channels, baselines);
+    KSP_TRY(ksp_pairs_same_or_apart({in, out}, channels, baselines));
+    KSP_TRY(ksp_pairs_same_or_apart(pairs, channels, baselines));
+    const ksp_tile_geometry geom =
+        ksp_make_tile_geometry(channels, baselines, AG_THREADS, AG_THREADS, AG_TARGET_GROUPS);
     KSP_REQUIRE(geom.groups <= 0x7fffffffll, "array too large for one launch");
     // (the rows of gains are read element by element; inputs has a flag of its own)
     const int aligned =

@@ -33,7 +33,8 @@
 // on them in registers, where power-of-two strides on 8-byte words would collide on banks, and
 // stores them. The later stages run in LDS, a barrier apart: consecutive threads take
 // consecutive j, 2-way conflicts at half = 8 and 16 and none above. A transform of 4 runs both
-// stages in LDS. The twiddles are evaluated with the float64 series of predict.hip.
+// stages in LDS. The twiddles are evaluated with the float64 series of cal_math.h
+// (ksp_cos_sin_turns, which is cos_sin above).
 //
 // After the peak search the transform is dead and its LDS carries the sums across wavefronts.
 // The refinement reads x again from gains (L2): thread i owns channels i, i + T, i + 2 T, ...,
@@ -45,6 +46,7 @@
 // nor written.
 #include <cmath>
 
+#include "cal_math.h"
 #include "launch.h"
 
 #define FD_MIN_FFT 4
@@ -68,50 +70,19 @@ static size_t fd_lds_bytes(int n_fft)
     return transform > sums ? transform : sums;
 }
 
-// (cos, sin) of 2 pi x, every step as PredictHost.cos_sin has it (predict.hip: pr_cos_sin)
-__device__ __forceinline__ void fd_cos_sin(double x, double &co, double &si)
-{
-    const double r = __dsub_rn(x, rint(x));
-    const double q = rint(__dmul_rn(4.0, r));
-    const double y = __dsub_rn(r, __dmul_rn(q, 0.25));
-    const double z = __dmul_rn(y, 6.283185307179586);
-    const double z2 = __dmul_rn(z, z);
-    double sn = -2.505210838544172e-08;
-    sn = __dadd_rn(__dmul_rn(sn, z2), 2.7557319223985893e-06);
-    sn = __dadd_rn(__dmul_rn(sn, z2), -0.0001984126984126984);
-    sn = __dadd_rn(__dmul_rn(sn, z2), 0.008333333333333333);
-    sn = __dadd_rn(__dmul_rn(sn, z2), -0.16666666666666666);
-    sn = __dadd_rn(__dmul_rn(sn, z2), 1.0);
-    sn = __dmul_rn(sn, z);
-    double cs = 2.08767569878681e-09;
-    cs = __dadd_rn(__dmul_rn(cs, z2), -2.755731922398589e-07);
-    cs = __dadd_rn(__dmul_rn(cs, z2), 2.48015873015873e-05);
-    cs = __dadd_rn(__dmul_rn(cs, z2), -0.001388888888888889);
-    cs = __dadd_rn(__dmul_rn(cs, z2), 0.041666666666666664);
-    cs = __dadd_rn(__dmul_rn(cs, z2), -0.5);
-    cs = __dadd_rn(__dmul_rn(cs, z2), 1.0);
-    const bool odd = q == 1.0 || q == -1.0, half = q == 2.0 || q == -2.0;
-    co = odd ? sn : cs;
-    si = odd ? cs : sn;
-    co = q == 1.0 || half ? -co : co;
-    si = q == -1.0 || half ? -si : si;
-}
-
 // The twiddle of butterfly j of stage s: j < 2^(s-1), so the quotient is exact
 __device__ __forceinline__ float2 fd_twiddle(int j, int s)
 {
     double co, si;
-    fd_cos_sin(__dmul_rn((double)j, 1.0 / (double)(1 << s)), co, si);
+    ksp_cos_sin_turns(__dmul_rn((double)j, 1.0 / (double)(1 << s)), co, si);
     return make_float2((float)co, (float)-si);
 }
 
 __device__ __forceinline__ void fd_butterfly(float2 &a, float2 &b, float2 tw)
 {
-    const float bt_re = __fsub_rn(__fmul_rn(b.x, tw.x), __fmul_rn(b.y, tw.y));
-    const float bt_im = __fadd_rn(__fmul_rn(b.x, tw.y), __fmul_rn(b.y, tw.x));
-    const float2 a0 = a;
-    a = make_float2(__fadd_rn(a0.x, bt_re), __fadd_rn(a0.y, bt_im));
-    b = make_float2(__fsub_rn(a0.x, bt_re), __fsub_rn(a0.y, bt_im));
+    const float2 bt = ksp_cmul(b, tw), a0 = a;
+    a = make_float2(__fadd_rn(a0.x, bt.x), __fadd_rn(a0.y, bt.y));
+    b = make_float2(__fsub_rn(a0.x, bt.x), __fsub_rn(a0.y, bt.y));
 }
 
 // x[c] of input p, and whether the channel is kept (c < channels)
@@ -163,7 +134,7 @@ __device__ fd_sums fd_pass(const float2 *gains, const uint8_t *status, long long
             if (kept) {
                 const double cd = (double)c, xr = (double)x.x, xi = (double)x.y;
                 double co, si;
-                fd_cos_sin(__dmul_rn(cd, nu), co, si);
+                ksp_cos_sin_turns(__dmul_rn(cd, nu), co, si);
                 const double er = __dadd_rn(__dmul_rn(xr, co), __dmul_rn(xi, si));
                 const double ei = __dsub_rn(__dmul_rn(xi, co), __dmul_rn(xr, si));
                 const double c2 = __dmul_rn(cd, cd);
@@ -298,8 +269,7 @@ __global__ __launch_bounds__(FD_MAX_THREADS) void fit_delays_kernel(
     float peak = -1.0f;  // (no power is negative)
     int k0 = 0x7fffffff;
     for (int k = tid; k < n_fft; k += threads) {
-        const float2 t = X[k];
-        const float power = __fadd_rn(__fmul_rn(t.x, t.x), __fmul_rn(t.y, t.y));
+        const float power = ksp_norm2(X[k]);
         if (power > peak) {  // (k ascends within a thread)
             peak = power;
             k0 = k;
@@ -382,7 +352,7 @@ __global__ __launch_bounds__(FD_MAX_THREADS) void fit_delays_kernel(
             float2 out = make_float2(nan32, nan32);
             if (!no_fit) {
                 double co, si;
-                fd_cos_sin(__dmul_rn((double)c, nu), co, si);
+                ksp_cos_sin_turns(__dmul_rn((double)c, nu), co, si);
                 out.x = (float)__dsub_rn(__dmul_rn(wide_re, co), __dmul_rn(wide_im, si));
                 out.y = (float)__dadd_rn(__dmul_rn(wide_re, si), __dmul_rn(wide_im, co));
                 if (corrections) out.y = -out.y;
@@ -417,18 +387,15 @@ extern "C" int ksp_fit_delays(int device, void *stream, const void *gains, const
     KSP_REQUIRE(std::isfinite(channel_width) && channel_width != 0.0,
                 "channel_width must be finite and not 0");
     KSP_TRY(ksp_planes_hold({p_gains, p_model}, n_inputs, "n_inputs"));
-    if (model != nullptr) {
-        const uintptr_t g0 = (uintptr_t)gains, m0 = (uintptr_t)model;
-        const uintptr_t g1 = g0 + (uintptr_t)(((channels - 1ll) * gains_stride + n_inputs) * 8);
-        const uintptr_t m1 = m0 + (uintptr_t)(((channels - 1ll) * model_stride + n_inputs) * 8);
-        KSP_REQUIRE(g1 <= m0 || m1 <= g0, "model overlaps gains");
-    }
+    KSP_REQUIRE(model == nullptr || ksp_planes_apart(p_model, channels, n_inputs, p_gains,
+                                                     channels, n_inputs),
+                "model overlaps gains");
 
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
-    int log2_fft = 0, c_pad = 1;
+    int log2_fft = 0;
     while ((1 << log2_fft) < n_fft) log2_fft++;
-    while (c_pad < channels) c_pad *= 2;
+    const int c_pad = ksp_next_pow2(channels);
     const int variant = (status != nullptr ? 1 : 0) | (model != nullptr ? 2 : 0);
     int rc = 0;
     ksp_dispatch_exact<0, 1, 2, 3>(variant, [&](auto V) {

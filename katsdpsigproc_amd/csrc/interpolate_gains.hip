@@ -47,6 +47,7 @@
 // the workgroup. An input is read completely before the first store, so `out` may be `gains`.
 // Row offsets are size_t. No atomics, no workspace, no dependence on the order of workgroups.
 // Padding is neither read nor written.
+#include "cal_math.h"
 #include "launch.h"
 
 #define IG_MAX_CHANNELS 16384
@@ -62,27 +63,9 @@
 
 typedef unsigned long long ig_word;
 
-static int ig_c_pad(int channels)
-{
-    int c_pad = 1;
-    while (c_pad < channels) c_pad *= 2;
-    return c_pad;
-}
 static int ig_threads(int c_pad)
 {
     return c_pad < 64 ? 64 : c_pad > IG_MAX_THREADS ? IG_MAX_THREADS : c_pad;
-}
-
-__device__ __forceinline__ bool ig_finite(float2 v)
-{
-    return __builtin_isfinite(v.x) && __builtin_isfinite(v.y);
-}
-
-// a b
-__device__ __forceinline__ float2 ig_mul(float2 a, float2 b)
-{
-    return make_float2(__fsub_rn(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)),
-                       __fadd_rn(__fmul_rn(a.x, b.y), __fmul_rn(a.y, b.x)));
 }
 
 __device__ __forceinline__ int ig_highest(ig_word word) { return 63 - __clzll((long long)word); }
@@ -118,14 +101,13 @@ __global__ __launch_bounds__(IG_MAX_THREADS) void interpolate_gains_kernel(
             bool keep = false;
             if (c < channels) {
                 float2 d = gains[(size_t)c * gains_stride + p];
-                keep = ig_finite(d);
+                keep = ksp_cfinite(d);
                 if (status != nullptr) keep = keep && (status[c] & mask) == 0;
                 if (model != nullptr) {
                     const float2 mc = model[(size_t)c * model_stride + p];
                     mm[m] = mc;
-                    keep = keep && ig_finite(mc);
-                    d = make_float2(__fadd_rn(__fmul_rn(d.x, mc.x), __fmul_rn(d.y, mc.y)),
-                                    __fsub_rn(__fmul_rn(d.y, mc.x), __fmul_rn(d.x, mc.y)));
+                    keep = keep && ksp_cfinite(mc);
+                    d = ksp_cmul_conj(d, mc);
                 }
                 ig_col[c] = d;
             }
@@ -213,7 +195,7 @@ __global__ __launch_bounds__(IG_MAX_THREADS) void interpolate_gains_kernel(
             const int c = tid + m * threads;
             if (m < per_thread && c < channels && (words[c >> 6] >> (c & 63) & 1) != 0) {
                 const float2 s = ig_col[c];
-                term[m] = __builtin_sqrtf(__fadd_rn(__fmul_rn(s.x, s.x), __fmul_rn(s.y, s.y)));
+                term[m] = __builtin_sqrtf(ksp_norm2(s));
             }
         }
         // the levels of the tree whose two terms belong to one thread: i + m T with i + (m + n) T
@@ -296,13 +278,9 @@ __global__ __launch_bounds__(IG_MAX_THREADS) void interpolate_gains_kernel(
                     n_filled += got;
                     gap_left |= !got;
                 }
-                if (model != nullptr) y = ig_mul(y, mm[m]);
-                if (scale != nullptr) y = ig_mul(y, factor);
-                if (corrections) {
-                    const float q = __fadd_rn(__fmul_rn(y.x, y.x), __fmul_rn(y.y, y.y));
-                    y = q > 0.0f ? make_float2(__fdiv_rn(y.x, q), __fdiv_rn(-y.y, q))
-                                 : make_float2(nan32, nan32);
-                }
+                if (model != nullptr) y = ksp_cmul(y, mm[m]);
+                if (scale != nullptr) y = ksp_cmul(y, factor);
+                if (corrections) y = ksp_creciprocal_or_nan(y);
             }
             out[(size_t)c * out_stride + p] = y;
         }
@@ -356,20 +334,16 @@ extern "C" int ksp_interpolate_gains(int device, void *stream, const void *gains
     KSP_REQUIRE(status_mask >= 0 && status_mask <= 255, "status_mask must be 0..255");
     KSP_REQUIRE(corrections == 0 || corrections == 1, "corrections must be 0 or 1");
     KSP_TRY(ksp_planes_hold({p_gains, p_model, p_out}, n_inputs, "n_inputs"));
-    KSP_REQUIRE(ksp_same_or_apart(gains, gains_stride, out, out_stride, channels, n_inputs, 8),
-                "out overlaps gains without being gains with the same stride");
-    if (model != nullptr) {
-        const uintptr_t o0 = (uintptr_t)out, m0 = (uintptr_t)model;
-        const uintptr_t o1 = o0 + (uintptr_t)(((channels - 1ll) * out_stride + n_inputs) * 8);
-        const uintptr_t m1 = m0 + (uintptr_t)(((channels - 1ll) * model_stride + n_inputs) * 8);
-        KSP_REQUIRE(o1 <= m0 || m1 <= o0, "out overlaps model");
-    }
+    KSP_TRY(ksp_pairs_same_or_apart({p_gains, p_out}, channels, n_inputs));
+    KSP_REQUIRE(model == nullptr ||
+                    ksp_planes_apart(p_out, channels, n_inputs, p_model, channels, n_inputs),
+                "out overlaps model");
 
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
     constexpr auto kernel = interpolate_gains_kernel;
     KSP_TRY(ksp_lds_opt_in<kernel>(device, 8 * (size_t)IG_MAX_CHANNELS));
-    const int c_pad = ig_c_pad(channels), threads = ig_threads(c_pad);
+    const int c_pad = ksp_next_pow2(channels), threads = ig_threads(c_pad);
     const int per_thread = (channels + threads - 1) / threads;
     hipLaunchKernelGGL(kernel, dim3((unsigned)n_inputs), dim3(threads), 8 * (size_t)channels, s,
                        (const float2 *)gains, status, (const float2 *)model,

@@ -32,6 +32,13 @@ void ksp_set_error(const char *fmt, ...);
 #define KSP_LAUNCH_CHECK() KSP_CHECK(hipGetLastError())
 
 static inline int ksp_divup(int a, int b) { return (a + b - 1) / b; }
+// The lowest power of two at or above n (1 for n <= 1; n at most 2^30)
+static inline int ksp_next_pow2(int n)
+{
+    int p = 1;
+    while (p < n) p *= 2;
+    return p;
+}
 
 #ifdef __HIPCC__
 // Correctly rounded float32 square root for 1 <= x <= 2 (NaN passes through): one

@@ -94,16 +94,46 @@ inline bool ksp_planes_aligned(ksp_planes planes)
     return true;
 }
 
-// Whether the [rows][stride] array `out` is `in` itself (same pointer, same stride: in place) or
-// shares no byte with it; `cols` elements of `elem_bytes` bytes per row are data.
-inline bool ksp_same_or_apart(const void *in, long long in_stride, const void *out,
-                              long long out_stride, int rows, int cols, int elem_bytes)
+// Whether two planes, each with its rows and the columns of a row that are data, share no byte.
+inline bool ksp_planes_apart(const ksp_plane &a, long long a_rows, long long a_cols,
+                             const ksp_plane &b, long long b_rows, long long b_cols)
 {
-    if (in == out && in_stride == out_stride) return true;
-    const uintptr_t a0 = (uintptr_t)in, b0 = (uintptr_t)out;
-    const uintptr_t a1 = a0 + (uintptr_t)(((rows - 1ll) * in_stride + cols) * elem_bytes);
-    const uintptr_t b1 = b0 + (uintptr_t)(((rows - 1ll) * out_stride + cols) * elem_bytes);
+    const uintptr_t a0 = (uintptr_t)a.ptr, b0 = (uintptr_t)b.ptr;
+    const uintptr_t a1 = a0 + (uintptr_t)(((a_rows - 1) * a.stride + a_cols) * a.elem_bytes);
+    const uintptr_t b1 = b0 + (uintptr_t)(((b_rows - 1) * b.stride + b_cols) * b.elem_bytes);
     return a1 <= b0 || b1 <= a0;
+}
+
+// The inputs of a kernel that an output each goes with, as a list {in, out, in, out, ...}: an
+// optional input and its output are given together or not at all, and an output is its input
+// (same pointer, same stride: in place) or shares no byte with it. The two checks are apart
+// because a launcher has others between them.
+// "<in> and <out> must both be NULL or both be given" for the first pair with one of the two.
+inline int ksp_pairs_given_together(ksp_planes pairs)
+{
+    for (const ksp_plane *p = pairs.begin(); p != pairs.end(); p += 2)
+        if ((p[0].ptr == nullptr) != (p[1].ptr == nullptr)) {
+            ksp_set_error(
+                "invalid argument: %s and %s must both be NULL or both be given "
+                "((%s == nullptr) == (%s == nullptr))",
+                p[0].name, p[1].name, p[0].name, p[1].name);
+            return (int)hipErrorInvalidValue;
+        }
+    return 0;
+}
+
+// "<out> overlaps <in> without being <in> with the same stride" for the first given pair that
+// is neither; `cols` elements of each of the `rows` rows are data.
+inline int ksp_pairs_same_or_apart(ksp_planes pairs, long long rows, long long cols)
+{
+    for (const ksp_plane *p = pairs.begin(); p != pairs.end(); p += 2)
+        if (p[0].ptr != nullptr && !(p[0].ptr == p[1].ptr && p[0].stride == p[1].stride) &&
+            !ksp_planes_apart(p[0], rows, cols, p[1], rows, cols)) {
+            ksp_set_error("invalid argument: %s overlaps %s without being %s with the same stride",
+                          p[1].name, p[0].name, p[0].name);
+            return (int)hipErrorInvalidValue;
+        }
+    return 0;
 }
 
 // The grid of a kernel whose threads each take a run of `run` adjacent columns of one row,

@@ -7,15 +7,7 @@
 //
 //   per channel c, baseline j and source s = 0 .. n_sources - 1, in float64:
 //     x  = freqs[c] * delays[s][j]                 turns
-//     r  = x - rint(x);  q = rint(4 * r);  y = r - q * 0.25;  z = y * 6.283185307179586
-//     z2 = z * z
-//     sn = (((((S5*z2 + S4)*z2 + S3)*z2 + S2)*z2 + S1)*z2 + S0) * z
-//     cs = (((((C6*z2 + C5)*z2 + C4)*z2 + C3)*z2 + C2)*z2 + C1)*z2 + C0
-//       S0..S5 = 1.0, -0.16666666666666666, 0.008333333333333333, -0.0001984126984126984,
-//                2.7557319223985893e-06, -2.505210838544172e-08
-//       C0..C6 = 1.0, -0.5, 0.041666666666666664, -0.001388888888888889, 2.48015873015873e-05,
-//                -2.755731922398589e-07, 2.08767569878681e-09
-//     (co, si) = (cs, sn), (-sn, cs), (-cs, -sn), (sn, -cs)   for q = 0, 1, +-2, -1
+//     (co, si) = cos_sin(x)                        (cal_math.h: ksp_cos_sin_turns, the series)
 //     re += flux[c][s] * co;  im -= flux[c][s] * si           from +0, s ascending
 //   M = (float32(re), float32(im)) = model[c][j]; then, with vis, in float32:
 //     d  = M.re * M.re + M.im * M.im;  ok = 0 < d < inf
@@ -28,7 +20,7 @@
 // of the run in registers. A workgroup of 256 threads owns a tile of `tile_runs` runs (a power
 // of two, 1 .. PR_TILE_RUNS = 16: the narrowest that holds a row, so a tile is at most 256
 // baselines wide) and a chunk of `chunk` rows; thread t owns run t % tile_runs of the tile and,
-// of every batch of 256 / tile_runs rows, row t / tile_runs.
+// of every batch of 256 / tile_runs rows, row t / tile_runs (tile_grid.h).
 //
 // The delays of the tile are staged in LDS, PR_BLOCK = 16 sources at a time (32 KiB), element
 // i of run r of source s at word s * 256 + i * 16 + r whatever the tile's width: the lanes of
@@ -52,8 +44,10 @@
 // tile; per row of a lane 8 bytes of freqs and 4 bytes of flux per source, from L2.
 #include <cmath>
 
+#include "cal_math.h"
 #include "launch.h"
 #include "run16.h"
+#include "tile_grid.h"
 
 #define PR_THREADS 256
 #define PR_TILE_RUNS 16    // runs of a tile at most
@@ -62,69 +56,14 @@
 #ifndef PR_TARGET_GROUPS  // (an experiment's -D, KSP_EXTRA_HIPCC_FLAGS)
 #define PR_TARGET_GROUPS 4096
 #endif
-// float64 instructions per (sample, source) as written below: x (1), r (2), q (2), y (2),
-// z and z2 (2), sn (11), cs (12), the two products and the two sums (4)
+// float64 instructions per (sample, source) as written below and in ksp_cos_sin_turns: x (1),
+// r (2), q (2), y (2), z and z2 (2), sn (11), cs (12), the two products and the two sums (4)
 #define PR_FLOPS_PER_PAIR 36
 
 #define PR_MODEL 1
 #define PR_DIVIDE 2
 #define PR_WEIGHTS 4
 #define PR_FLAGS 8
-
-struct pr_geometry {
-    int tile_shift;  // log2(tile_runs)
-    int tiles;       // tiles per row
-    int chunk;       // rows per workgroup
-    long long groups;
-};
-
-// (groups stays below 3 * PR_TARGET_GROUPS + tiles, and tiles is at most 2^23)
-static pr_geometry pr_make_geometry(int channels, int baselines)
-{
-    pr_geometry g;
-    const int runs_per_row = (int)(((long long)baselines + KSP_RUN - 1) / KSP_RUN);
-    g.tile_shift = 0;
-    while ((1 << g.tile_shift) < PR_TILE_RUNS && (1 << g.tile_shift) < runs_per_row) g.tile_shift++;
-    const int tile_runs = 1 << g.tile_shift;
-    g.tiles = (runs_per_row + tile_runs - 1) / tile_runs;
-    const int slots = PR_THREADS / tile_runs;  // rows a workgroup works on at once
-    long long chunk = (long long)channels * g.tiles / PR_TARGET_GROUPS / slots * slots;
-    if (chunk > channels) chunk = channels;  // (wide rows: the tiles alone are groups enough)
-    if (chunk < slots) chunk = slots;
-    g.chunk = (int)chunk;
-    g.groups = (channels + chunk - 1) / chunk * g.tiles;
-    return g;
-}
-
-// (cos, sin) of 2 pi x, every step as the header comment has it
-__device__ __forceinline__ void pr_cos_sin(double x, double &co, double &si)
-{
-    const double r = __dsub_rn(x, rint(x));
-    const double q = rint(__dmul_rn(4.0, r));
-    const double y = __dsub_rn(r, __dmul_rn(q, 0.25));
-    const double z = __dmul_rn(y, 6.283185307179586);
-    const double z2 = __dmul_rn(z, z);
-    double sn = -2.505210838544172e-08;
-    sn = __dadd_rn(__dmul_rn(sn, z2), 2.7557319223985893e-06);
-    sn = __dadd_rn(__dmul_rn(sn, z2), -0.0001984126984126984);
-    sn = __dadd_rn(__dmul_rn(sn, z2), 0.008333333333333333);
-    sn = __dadd_rn(__dmul_rn(sn, z2), -0.16666666666666666);
-    sn = __dadd_rn(__dmul_rn(sn, z2), 1.0);
-    sn = __dmul_rn(sn, z);
-    double cs = 2.08767569878681e-09;
-    cs = __dadd_rn(__dmul_rn(cs, z2), -2.755731922398589e-07);
-    cs = __dadd_rn(__dmul_rn(cs, z2), 2.48015873015873e-05);
-    cs = __dadd_rn(__dmul_rn(cs, z2), -0.001388888888888889);
-    cs = __dadd_rn(__dmul_rn(cs, z2), 0.041666666666666664);
-    cs = __dadd_rn(__dmul_rn(cs, z2), -0.5);
-    cs = __dadd_rn(__dmul_rn(cs, z2), 1.0);
-    // q is -2 .. 2, or NaN, which takes the first row of the table with NaN in both
-    const bool odd = q == 1.0 || q == -1.0, half = q == 2.0 || q == -2.0;
-    co = odd ? sn : cs;
-    si = odd ? cs : sn;
-    co = q == 1.0 || half ? -co : co;
-    si = q == -1.0 || half ? -si : si;
-}
 
 template <int VARIANT>
 __global__ __launch_bounds__(PR_THREADS) void predict_kernel(
@@ -141,19 +80,13 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(
     constexpr bool HAS_W = VARIANT & PR_WEIGHTS, HAS_F = VARIANT & PR_FLAGS;
     __shared__ double staged[PR_BLOCK * PR_TILE_RUNS * KSP_RUN];
     const int tid = threadIdx.x;
-    const int tile = blockIdx.x % tiles;
-    const long long row_begin = (long long)(blockIdx.x / tiles) * chunk;
-    const long long row_end = min((long long)channels, row_begin + chunk);
-
-    const int tile_runs = 1 << tile_shift;
-    const int tile_cols = tile_runs * KSP_RUN;
-    const int run = tid & (tile_runs - 1);
-    const int slot = tid >> tile_shift;
-    const int slots = PR_THREADS >> tile_shift;
-    const long long tile_col0 = (long long)tile * tile_cols;
-    const long long col0 = tile_col0 + run * KSP_RUN;
-    // elements of the run inside the row: 0 for a lane beyond it, which then only helps to stage
-    const int valid = (int)min((long long)KSP_RUN, max(0ll, baselines - col0));
+    const ksp_tile_place at =
+        ksp_tile_locate(PR_THREADS, tiles, tile_shift, chunk, channels, baselines);
+    const long long row_begin = at.row_begin, row_end = at.row_end;
+    const long long tile_col0 = at.tile_col0, col0 = at.col0;
+    const int tile_cols = KSP_RUN << tile_shift;
+    const int run = at.run, slot = at.slot, slots = at.slots;
+    const int valid = at.valid;  // (0: the lane only helps to stage)
 
     // Sources s0 .. s0 + n - 1 of the tile into LDS; columns beyond the row are +0 and never
     // read from memory. Consecutive threads take consecutive baselines of one source.
@@ -193,7 +126,7 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(
 #pragma unroll
                     for (int i = 0; i < KSP_RUN; i++) {
                         double co, si;
-                        pr_cos_sin(__dmul_rn(f, d[i * PR_TILE_RUNS]), co, si);
+                        ksp_cos_sin_turns(__dmul_rn(f, d[i * PR_TILE_RUNS]), co, si);
                         re[i] = __dadd_rn(re[i], __dmul_rn(F, co));
                         im[i] = __dsub_rn(im[i], __dmul_rn(F, si));
                     }
@@ -217,8 +150,10 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(
 #pragma unroll
             for (int i = 0; i < KSP_RUN; i++) {
                 const float mr = m[i].x, mi = m[i].y;
-                const float d = __fadd_rn(__fmul_rn(mr, mr), __fmul_rn(mi, mi));
+                const float d = ksp_norm2(m[i]);
                 const bool ok = d > 0.0f && d < INFINITY;
+                // (ksp_cmul_conj(v[i], m[i]) written out: through the helper the compiler allots
+                // other registers to three of the variants, 120 to 132 for one)
                 const float nr = __fadd_rn(__fmul_rn(v[i].x, mr), __fmul_rn(v[i].y, mi));
                 const float ni = __fsub_rn(__fmul_rn(v[i].y, mr), __fmul_rn(v[i].x, mi));
                 v[i].x = ok ? __fdiv_rn(nr, d) : v[i].x;
@@ -229,26 +164,11 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(
             ksp_run_store(out_vis + row * out_vis_stride + col0, valid, wide, v);
             if (HAS_W) ksp_run_store(out_weights + row * out_weights_stride + col0, valid, wide, w);
             if (HAS_F) {
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    // bit k of the nibble to bit 0 of byte k (no two products share a bit)
-                    const unsigned spread = (((bad >> (4 * q)) & 0xfu) * 0x00204081u) & 0x01010101u;
-                    fl[q] |= spread * flag_value;
-                }
+                ksp_flag_spread(fl, bad, flag_value);
                 ksp_run_store_bytes(out_flags + row * out_flags_stride + col0, valid, wide, fl);
             }
         }
     }
-}
-
-// Whether two planes, each with its rows and the columns of a row that are data, share no byte
-static bool pr_apart(const ksp_plane &a, long long a_rows, long long a_cols, const ksp_plane &b,
-                     long long b_rows, long long b_cols)
-{
-    const uintptr_t a0 = (uintptr_t)a.ptr, b0 = (uintptr_t)b.ptr;
-    const uintptr_t a1 = a0 + (uintptr_t)(((a_rows - 1) * a.stride + a_cols) * a.elem_bytes);
-    const uintptr_t b1 = b0 + (uintptr_t)(((b_rows - 1) * b.stride + b_cols) * b.elem_bytes);
-    return a1 <= b0 || b1 <= a0;
 }
 
 extern "C" int ksp_predict(int device, void *stream, const double *freqs, const double *delays,
@@ -271,12 +191,7 @@ extern "C" int ksp_predict(int device, void *stream, const double *freqs, const 
     const ksp_planes data = {p_vis, p_out_vis, p_weights, p_out_weights, p_flags, p_out_flags};
     KSP_TRY(ksp_planes_given({p_freqs, p_delays, p_flux}));
     KSP_REQUIRE(model != nullptr || vis != nullptr, "model and vis must not both be NULL");
-    KSP_REQUIRE((vis == nullptr) == (out_vis == nullptr),
-                "vis and out_vis must both be NULL or both be given");
-    KSP_REQUIRE((weights == nullptr) == (out_weights == nullptr),
-                "weights and out_weights must both be NULL or both be given");
-    KSP_REQUIRE((flags == nullptr) == (out_flags == nullptr),
-                "flags and out_flags must both be NULL or both be given");
+    KSP_TRY(ksp_pairs_given_together(data));
     KSP_REQUIRE(weights == nullptr || vis != nullptr, "weights needs vis");
     KSP_REQUIRE(flags == nullptr || vis != nullptr, "flags needs vis");
     KSP_REQUIRE(channels >= 1, "channels must be at least 1");
@@ -287,31 +202,23 @@ extern "C" int ksp_predict(int device, void *stream, const double *freqs, const 
     KSP_TRY(ksp_planes_hold({p_flux}, n_sources, "n_sources"));
     KSP_TRY(ksp_planes_hold({p_model}, baselines, "baselines"));
     KSP_TRY(ksp_planes_hold(data, baselines, "baselines"));
-    KSP_REQUIRE(vis == nullptr || ksp_same_or_apart(vis, vis_stride, out_vis, out_vis_stride,
-                                                    channels, baselines, 8),
-                "out_vis overlaps vis without being vis with the same stride");
-    KSP_REQUIRE(weights == nullptr ||
-                    ksp_same_or_apart(weights, weights_stride, out_weights, out_weights_stride,
-                                      channels, baselines, 4),
-                "out_weights overlaps weights without being weights with the same stride");
-    KSP_REQUIRE(flags == nullptr || ksp_same_or_apart(flags, flags_stride, out_flags,
-                                                      out_flags_stride, channels, baselines, 1),
-                "out_flags overlaps flags without being flags with the same stride");
+    KSP_TRY(ksp_pairs_same_or_apart(data, channels, baselines));
     if (model != nullptr) {
-        KSP_REQUIRE(pr_apart(p_model, channels, baselines, p_freqs, 1, channels),
+        KSP_REQUIRE(ksp_planes_apart(p_model, channels, baselines, p_freqs, 1, channels),
                     "model overlaps freqs");
-        KSP_REQUIRE(pr_apart(p_model, channels, baselines, p_delays, n_sources, baselines),
+        KSP_REQUIRE(ksp_planes_apart(p_model, channels, baselines, p_delays, n_sources, baselines),
                     "model overlaps delays");
-        KSP_REQUIRE(pr_apart(p_model, channels, baselines, p_flux, channels, n_sources),
+        KSP_REQUIRE(ksp_planes_apart(p_model, channels, baselines, p_flux, channels, n_sources),
                     "model overlaps flux");
         for (const ksp_plane &other : data)
             if (other.ptr != nullptr &&
-                !pr_apart(p_model, channels, baselines, other, channels, baselines)) {
+                !ksp_planes_apart(p_model, channels, baselines, other, channels, baselines)) {
                 ksp_set_error("invalid argument: model overlaps %s", other.name);
                 return (int)hipErrorInvalidValue;
             }
     }
-    const pr_geometry geom = pr_make_geometry(channels, baselines);
+    const ksp_tile_geometry geom =
+        ksp_make_tile_geometry(channels, baselines, PR_THREADS, PR_TILE_RUNS, PR_TARGET_GROUPS);
     KSP_REQUIRE(geom.groups <= 0x7fffffffll, "array too large for one launch");
     const bool wide = ksp_planes_aligned({p_model}) && ksp_planes_aligned(data);
 

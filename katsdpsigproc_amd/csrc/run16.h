@@ -73,6 +73,17 @@ __device__ __forceinline__ ksp_run_bytes ksp_run_load_bytes(const uint8_t *p, in
     return ksp_run_bytes{w[0], w[1], w[2], w[3]};
 }
 
+// f[i] |= flag_value for every element i of the run whose bit of `bad` is set.
+__device__ __forceinline__ void ksp_flag_spread(ksp_run_bytes &f, unsigned bad, unsigned flag_value)
+{
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        // bit k of the nibble to bit 0 of byte k (no two products share a bit)
+        const unsigned spread = (((bad >> (4 * q)) & 0xfu) * 0x00204081u) & 0x01010101u;
+        f[q] |= spread * flag_value;
+    }
+}
+
 __device__ __forceinline__ void ksp_run_store_bytes(uint8_t *p, int valid, bool wide,
                                                     ksp_run_bytes w)
 {

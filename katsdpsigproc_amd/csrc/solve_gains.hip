@@ -36,6 +36,7 @@
 // The workgroup has n * ceil(n / 32) threads rounded up to whole wavefronts: 64 for up to 32
 // inputs, 128 for 64, 512 for 128. No atomics, no workspace, no dependence on the order of
 // workgroups. The sample arrays have any row stride; padding is neither read nor written.
+#include "cal_math.h"
 #include "launch.h"
 
 #define SG_MAX_INPUTS 128
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(512) void solve_gains_kernel(
         if (HAS_I) g0 = initial[c * stride.initial + tid];
         g_re[tid] = g0.x;
         g_im[tid] = g0.y;
-        g_s[tid] = __fadd_rn(__fmul_rn(g0.x, g0.x), __fmul_rn(g0.y, g0.y));
+        g_s[tid] = ksp_norm2(g0);
         has[tid] = 0;
     }
     __syncthreads();
@@ -174,9 +175,9 @@ __global__ __launch_bounds__(512) void solve_gains_kernel(
                 float ai = off ? a_im[e] : 0.0f;
                 const float w = off ? a_w[e] : 0.0f;
                 if (p > q) ai = -ai;
-                const float gr = g_re[q], gi = g_im[q];
-                nr = __fadd_rn(nr, __fsub_rn(__fmul_rn(ar, gr), __fmul_rn(ai, gi)));
-                ni = __fadd_rn(ni, __fadd_rn(__fmul_rn(ar, gi), __fmul_rn(ai, gr)));
+                const float2 ag = ksp_cmul(make_float2(ar, ai), make_float2(g_re[q], g_im[q]));
+                nr = __fadd_rn(nr, ag.x);
+                ni = __fadd_rn(ni, ag.y);
                 dn = __fadd_rn(dn, __fmul_rn(w, g_s[q]));
             }
             part_re[b * n + p] = nr;
@@ -201,13 +202,12 @@ __global__ __launch_bounds__(512) void solve_gains_kernel(
                 new_re = __fmul_rn(__fadd_rn(new_re, old_re), 0.5f);
                 new_im = __fmul_rn(__fadd_rn(new_im, old_im), 0.5f);
                 const float dr = __fsub_rn(new_re, old_re), di = __fsub_rn(new_im, old_im);
-                d_term[tid] = has_p ? __fadd_rn(__fmul_rn(dr, dr), __fmul_rn(di, di)) : 0.0f;
-                n_term[tid] =
-                    has_p ? __fadd_rn(__fmul_rn(new_re, new_re), __fmul_rn(new_im, new_im)) : 0.0f;
+                d_term[tid] = has_p ? ksp_norm2(make_float2(dr, di)) : 0.0f;
+                n_term[tid] = has_p ? ksp_norm2(make_float2(new_re, new_im)) : 0.0f;
             }
             g_re[tid] = new_re;
             g_im[tid] = new_im;
-            g_s[tid] = __fadd_rn(__fmul_rn(new_re, new_re), __fmul_rn(new_im, new_im));
+            g_s[tid] = ksp_norm2(make_float2(new_re, new_im));
         }
         __syncthreads();
         if ((k & 1) == 0) {
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(512) void solve_gains_kernel(
     float u_re = 1.0f, u_im = 0.0f;
     if (reference >= 0) {
         const float r_re = g_re[reference], r_im = g_im[reference];
-        const float m = __builtin_sqrtf(__fadd_rn(__fmul_rn(r_re, r_re), __fmul_rn(r_im, r_im)));
+        const float m = __builtin_sqrtf(ksp_norm2(make_float2(r_re, r_im)));
         referenced = has[reference] != 0 && m > 0.0f && m < __builtin_inff();
         if (referenced) {
             u_re = __fdiv_rn(r_re, m);
@@ -247,22 +247,14 @@ __global__ __launch_bounds__(512) void solve_gains_kernel(
         }
     }
     if (tid < n) {
-        float re = g_re[tid], im = g_im[tid];
+        float2 g = make_float2(g_re[tid], g_im[tid]);
         if (referenced) {
-            const float t_re = __fsub_rn(__fmul_rn(re, u_re), __fmul_rn(im, u_im));
-            const float t_im = __fadd_rn(__fmul_rn(re, u_im), __fmul_rn(im, u_re));
-            re = t_re;
-            im = tid == reference ? 0.0f : t_im;
+            g = ksp_cmul(g, make_float2(u_re, u_im));
+            if (tid == reference) g.y = 0.0f;
         }
-        if (corrections) {
-            const float s = __fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im));
-            const bool pos = s > 0.0f;
-            const float c_re = __fdiv_rn(re, s), c_im = __fdiv_rn(-im, s);
-            re = pos ? c_re : __builtin_nanf("");
-            im = pos ? c_im : __builtin_nanf("");
-        }
-        if (!has_p) re = im = __builtin_nanf("");
-        gains[c * stride.gains + tid] = make_float2(re, im);
+        if (corrections) g = ksp_creciprocal_or_nan(g);
+        if (!has_p) g.x = g.y = __builtin_nanf("");
+        gains[c * stride.gains + tid] = g;
     }
     if (tid == 0) {
         iterations[c] = k;
@@ -282,9 +274,9 @@ extern "C" int ksp_solve_gains(int device, void *stream, const void *vis, const 
     const ksp_planes samples = {{"vis", vis, vis_stride, 8},
                                 {"weights", weights, weights_stride, 4, true},
                                 {"flags", flags, flags_stride, 1, true}};
-    const ksp_planes tables = {{"pairs", pairs, pairs_stride, 4},
-                               {"initial", initial, initial_stride, 8, true},
-                               {"gains", gains, gains_stride, 8}};
+    const ksp_plane p_initial = {"initial", initial, initial_stride, 8, true};
+    const ksp_plane p_gains = {"gains", gains, gains_stride, 8};
+    const ksp_planes tables = {{"pairs", pairs, pairs_stride, 4}, p_initial, p_gains};
     KSP_TRY(ksp_planes_given(samples));
     KSP_TRY(ksp_planes_given(tables));
     KSP_TRY(ksp_planes_given({{"iterations", iterations, 0, 4}, {"status", status, 0, 1}}));
@@ -299,9 +291,7 @@ extern "C" int ksp_solve_gains(int device, void *stream, const void *vis, const 
     KSP_REQUIRE(corrections == 0 || corrections == 1, "corrections must be 0 or 1");
     KSP_TRY(ksp_planes_hold(samples, baselines, "baselines"));
     KSP_TRY(ksp_planes_hold(tables, n_inputs, "n_inputs"));
-    KSP_REQUIRE(initial == nullptr || ksp_same_or_apart(initial, initial_stride, gains,
-                                                        gains_stride, channels, n_inputs, 8),
-                "gains overlaps initial without being initial with the same stride");
+    KSP_TRY(ksp_pairs_same_or_apart({p_initial, p_gains}, channels, n_inputs));
 
     KSP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;

@@ -15,7 +15,7 @@ from tests.test_gpu_prepare import N_AUTO, chain_dump
 
 pytestmark = pytest.mark.gpu
 
-# The sizes at which csrc/apply_gains.hip changes path (ag_make_geometry, ag_stage_rows).
+# The sizes at which csrc/apply_gains.hip changes path (ksp_make_tile_geometry, ag_stage_rows).
 # A lane owns a run of RUN baselines and a workgroup has THREADS lanes. A tile is the narrowest
 # power of two of runs that holds a row, at most THREADS of them: the tile width changes at
 # 16, 32, 64, ... and stays TILE = 4096 baselines from there on, so rows beyond 4096, 8192, ...

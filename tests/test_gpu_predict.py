@@ -15,7 +15,7 @@ from tests.test_gpu_prepare import LOST, N_AUTO
 
 pytestmark = pytest.mark.gpu
 
-# The sizes at which csrc/predict.hip changes path (pr_make_geometry, the staging of sources).
+# The sizes at which csrc/predict.hip changes path (ksp_make_tile_geometry, the staging of sources).
 # A lane owns a run of RUN baselines and a workgroup has THREADS lanes. A tile is the narrowest
 # power of two of runs that holds a row, at most TILE_RUNS = 16 of them: the tile width changes
 # at 16, 32, 64, 128 and stays TILE = 256 baselines from there on, so rows beyond 256, 512, ...

@@ -752,11 +752,18 @@ def test_header_binding_and_exports_agree(lib):
     for name in ("PredictTemplate", "Predict", "PredictHostFromDevice"):
         assert hasattr(ingest, name)
     assert hasattr(host, "PredictHost")
-    # the header comment, the host class and the kernel show the same digits
-    kernel = open(os.path.join(root, "katsdpsigproc_amd", "csrc", "predict.hip")).read()
+    # the header comment, the host class and the one copy of the series (in its comment and in
+    # its code) show the same digits; the kernel includes that copy and has none of its own
+    csrc = os.path.join(root, "katsdpsigproc_amd", "csrc")
+    series = open(os.path.join(csrc, "cal_math.h")).read()
+    kernel = open(os.path.join(csrc, "predict.hip")).read()
+    assert '#include "cal_math.h"' in kernel and "ksp_cos_sin_turns(" in kernel
     coefficients = host.PredictHost.SIN_COEFFICIENTS + host.PredictHost.COS_COEFFICIENTS
     for value in coefficients + (host.PredictHost.TWO_PI,):
-        assert repr(abs(value)) in comment and kernel.count(repr(abs(value))) >= 2, value
+        assert repr(abs(value)) in comment and series.count(repr(abs(value))) >= 2, value
+    for value in coefficients + (host.PredictHost.TWO_PI,):
+        if abs(value) not in (1.0, 0.5):  # (digits that text has for other reasons)
+            assert repr(abs(value)) not in kernel, value
     for k in range(6):
         assert host.PredictHost.SIN_COEFFICIENTS[k] == (-1) ** k / math.factorial(2 * k + 1)
     for k in range(7):
