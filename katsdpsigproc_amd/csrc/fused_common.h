@@ -833,6 +833,9 @@ __device__ __forceinline__ double mad_noise(const float (&dev)[R], int lane, dou
     int r = rank - below_bin;  // 0-based rank inside the bin
     unsigned long long cand = 0;
     const bool narrowed = in_bin > LIST_CAP;
+    // the smallest float32 pattern of the bin: of key K (the key is ceil(pattern / 65536), and
+    // K >= 1 here), or the one value that is left of it once it has been narrowed
+    unsigned bin_first = ((K - 1) << 16) + 1u;
     if (narrowed) {
         // Degenerate data (hundreds of samples in one key bin, e.g. quantised input):
         // narrow the bin with an exact search on the full float32 patterns, which
@@ -860,6 +863,7 @@ __device__ __forceinline__ double mad_noise(const float (&dev)[R], int lane, dou
         in_bin = ksp_wave_sum(__popcll(cand));
         r = rank - below;
         below_bin = below;
+        bin_first = cur;
         if (in_bin > LIST_CAP) {
             // Still too many: they share ONE float32 value, so their exact float64
             // values all lie within half a float32 ulp of it. Select among them
@@ -1065,16 +1069,17 @@ __device__ __forceinline__ double mad_noise(const float (&dev)[R], int lane, dou
     }
     if (even && !have_prev) {
         // r == 0: the lower median is the largest value below the bin. Its float32 value is
-        // the largest |dev| whose key is below K, i.e. whose pattern p is below
-        // T = ((K - 1) << 16) + 1 (the key is ceil(p / 65536), and K >= 1 here). All on the
-        // integer patterns: a NaN deviation, 0x7fc00000, stays above every T.
+        // the largest |dev| whose pattern p is below T = bin_first: every pattern of a smaller
+        // key, and after narrowing those of key K below the value kept as well (r counts from
+        // that value then, not from the start of the key's bin). All on the integer
+        // patterns: a NaN deviation, 0x7fc00000, stays above every T.
         // Pass 1, two instructions per sample: w = 2 p - 2 T modulo 2^32 (the doubling
         // drops the sign bit) lies in [2^32 - 2 T, 2^32 - 2] and grows with p for p < T,
         // and in [0, 2^32 - 2 - 2 T] for T <= p <= 0x7fffffff, so the unsigned maximum of
         // w, started at 2^32 - 2 T (p = 0), is 2 b - 2 T for b = max(p < T ? p : 0).
         // (Each dev[j] goes through an asm of its own, as dv() would have it: no key or
         // pattern of the search above is kept alive for this.)
-        const unsigned bias = 0u - 2u * (((K - 1) << 16) + 1u);
+        const unsigned bias = 0u - 2u * (unsigned)__builtin_amdgcn_readfirstlane((int)bin_first);
         unsigned wmax0 = bias, wmax1 = bias;
 #pragma unroll
         for (int j = 0; j < R; j++) {
@@ -1087,9 +1092,9 @@ __device__ __forceinline__ double mad_noise(const float (&dev)[R], int lane, dou
         }
         const unsigned b2 = ksp_wave_max(max(wmax0, wmax1)) - bias;  // 2 b
         const float b32 = __uint_as_float(b2 >> 1);
-        // (only samples with key 0 have pattern 0. Nothing with a non-zero key below the bin:
-        // the value below it is a +-2^-150 -- were there none, an even count could not have
-        // its lower median down here)
+        // (only samples with key 0 have pattern 0. Nothing that is not zero as float32 below
+        // the bin: the value below it is a +-2^-150 -- were there none, an even count could
+        // not have its lower median down here)
         const bool below_is_tiny = b2 == 0;
         // Pass 2, three per sample: which samples are at that value, 2 p == 2 b.
         // mask = 2 * mask + (compare): v_cmp into vcc, v_addc folds it in
