@@ -611,6 +611,47 @@ int ksp_solve_gains(int device, void *stream, const void *vis, const float *weig
                     int pairs_stride, int initial_stride, int gains_stride, int max_iterations,
                     float tol2, int reference, int mask, int corrections);
 
+/* solve_jones: per-antenna 2x2 Jones matrices solved per channel from averaged visibilities of
+ * an unpolarised unit source at the phase centre, with the full-polarisation StEFCal step, in
+ * one launch (no reference counterpart; bit for bit what rfi/host.py SolveJonesHost computes,
+ * whose docstring states every step and the order of the operations inside it; the rules for
+ * float steps and for sums are those of ksp_solve_gains).
+ * n_inputs is even; input 2a + i is feed i of antenna a. vis, weights, flags, pairs,
+ * iterations and status are as for ksp_solve_gains, with the same kept-sample rule and the same
+ * rules for an entry of pairs, and one more: an entry [p][q] with p / 2 == q / 2 (one antenna)
+ * is no baseline. initial: complex64 [channels][initial_stride][2] or NULL (every matrix the
+ * identity); jones: complex64 [channels][jones_stride][2]; row p = 2a + i holds
+ * z_p = (J_a[i][0], J_a[i][1]), and the model is V[p][q] = z_p[0] conj(z_q[0]) +
+ * z_p[1] conj(z_q[1]). initial_stride and jones_stride count rows of two complex64 (16
+ * bytes); the other strides count elements. Per channel, k = 1 .. max_iterations:
+ *   num[p] = sum_q A[p][q] z_q;  H[p] = sum_q W[p][q] z_q^H z_q (2x2, Hermitian);
+ *   new[p] = num[p] H[p]^-1 where det H[p] > 0, else z_p;
+ *   k odd: z = new;  k even: z = (new + z) / 2, and the channel stops, converged, when
+ *   sum_p |z_p - old_p|^2 <= tol2 * sum_p |z_p|^2 over the inputs that have data.
+ * Then, if reference >= 0 (an antenna), both of its inputs have data and the modulus of its
+ * matrix's determinant is positive and finite, every row is multiplied by U^H, U the unitary
+ * factor of that matrix's polar decomposition, which makes the reference's matrix Hermitian and
+ * positive, and the imaginary parts of its diagonal become +0 (for an unpolarised source this
+ * choice of U is a convention that the data cannot check); with corrections != 0 every
+ * antenna's matrix is replaced by its inverse adj(J) / det J (NaN where |det J|^2 is not > 0 or
+ * either input has no data); without corrections the rows of inputs without data are
+ * NaN + NaN j. status[c] has bit 0 for "not converged", bit 1 for "no input has data", bit 2
+ * for "not referenced" (reference == -1 included) and bit 3 for "in the last iteration an input
+ * with data kept its row because det H was not above 0".
+ * n_inputs is even and 2..128, max_iterations 1..1000, tol2 at least 0, reference
+ * -1..n_inputs/2-1, mask 0..255, corrections 0 or 1, channels and baselines at least 1. jones
+ * may be initial (the same pointer with the same stride); otherwise it must share no byte with
+ * it; both need the alignment of a complex64 only. Elements between baselines (or n_inputs)
+ * and a stride are neither read nor written. One workgroup per channel with the channel's
+ * matrix in LDS; one kernel launch, no workspace, no atomics. Every argument is checked before
+ * any device call. */
+int ksp_solve_jones(int device, void *stream, const void *vis, const float *weights,
+                    const uint8_t *flags, const int32_t *pairs, const void *initial, void *jones,
+                    int32_t *iterations, uint8_t *status, int channels, int baselines,
+                    int n_inputs, int vis_stride, int weights_stride, int flags_stride,
+                    int pairs_stride, int initial_stride, int jones_stride, int max_iterations,
+                    float tol2, int reference, int mask, int corrections);
+
 /* predict: model visibilities of up to 64 point sources and, optionally, the data divided by
  * them, in one launch: the step in front of ksp_solve_gains for a calibrator that is not a unit
  * source at the phase centre (no reference counterpart; bit for bit what rfi/host.py

@@ -1,5 +1,5 @@
-// Device arithmetic the calibration kernels share (apply_gains, solve_gains, predict, fit_delays,
-// interpolate_gains). Each kernel reproduces a host class of rfi/host.py bit for bit, so every
+// Device arithmetic the calibration kernels share (apply_gains, solve_gains, solve_jones, predict,
+// fit_delays, interpolate_gains). Each kernel reproduces a host class of rfi/host.py bit for bit, so every
 // helper is one float operation per written step, in the order written, with intrinsics that
 // are never contracted; a helper stands only where a kernel's expression is operation for
 // operation this one. Device code only.
@@ -40,6 +40,42 @@ __device__ __forceinline__ float2 ksp_creciprocal_or_nan(float2 a)
     const float nan32 = __builtin_nanf("");
     return q > 0.0f ? make_float2(__fdiv_rn(a.x, q), __fdiv_rn(-a.y, q))
                     : make_float2(nan32, nan32);
+}
+
+// ---- 2x2 complex float32 (host: SolveJonesHost; a matrix is [[a, b], [c, d]])
+
+// a + b,  a - b
+__device__ __forceinline__ float2 ksp_cadd(float2 a, float2 b)
+{
+    return make_float2(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y));
+}
+__device__ __forceinline__ float2 ksp_csub(float2 a, float2 b)
+{
+    return make_float2(__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y));
+}
+
+// the determinant a d - b c
+__device__ __forceinline__ float2 ksp_det2(float2 a, float2 b, float2 c, float2 d)
+{
+    return ksp_csub(ksp_cmul(a, d), ksp_cmul(b, c));
+}
+
+// (x, y) . conj((u, v)) = x conj(u) + y conj(v): a row times the conjugate of another
+__device__ __forceinline__ float2 ksp_row_dot_conj(float2 x, float2 y, float2 u, float2 v)
+{
+    return ksp_cadd(ksp_cmul_conj(x, u), ksp_cmul_conj(y, v));
+}
+
+// row `odd` of the adjugate [[d, -b], [-c, a]] times the scalar i: (d i, -(b i)) or
+// (-(c i), a i); the product is negated, not the factor (the sign of a zero differs)
+__device__ __forceinline__ void ksp_adj2_row_times(float2 a, float2 b, float2 c, float2 d,
+                                                   float2 i, bool odd, float2 &first,
+                                                   float2 &second)
+{
+    const float2 keep = ksp_cmul(odd ? a : d, i), turn = ksp_cmul(odd ? c : b, i);
+    const float2 minus = make_float2(-turn.x, -turn.y);
+    first = odd ? minus : keep;
+    second = odd ? keep : minus;
 }
 
 // ---- float64 (host: PredictHost.cos_sin)

@@ -985,6 +985,272 @@ class SolveGainsHost:
         return gains, iterations, status
 
 
+class SolveJonesHost(SolveGainsHost):
+    """Per-antenna 2x2 Jones matrices solved from averaged visibilities of an unpolarised unit
+    source at the phase centre, channel by channel, with the full-polarisation StEFCal step
+    (Salvini & Wijnholds 2014, section 4): the leakage solve that :class:`SolveGainsHost`, which
+    treats the two feeds of a dish as unrelated inputs, cannot do. No reference counterpart;
+    this class is the definition that the device operation (:class:`.ingest.SolveJonesTemplate`)
+    matches bit for bit.
+
+    ``n_inputs`` is even, 2..128; input ``2a + i`` is feed ``i`` of antenna ``a``. The arguments
+    are those of :class:`SolveGainsHost`, with the same kept-sample rule and the same rules for
+    an entry of ``pairs``, and one more: an entry whose two inputs belong to one antenna
+    (``p // 2 == q // 2``, the cross-feed autocorrelation) is treated as 0. ``A``, ``W`` and
+    "has data" are built as there. ``initial`` and the result ``jones`` are complex64
+    (channels, n_inputs, 2): row ``p = 2a + i`` is row ``i`` of antenna ``a``'s Jones matrix,
+    ``z_p = (J_a[i][0], J_a[i][1])``, and the model is ``V[p][q] = z_p[0] conj(z_q[0]) +
+    z_p[1] conj(z_q[1])``. Without `initial` every matrix starts as the identity.
+
+    Every float step is one float32 operation, rounded once, in the order written (never an
+    fma; real and imaginary parts apart; correctly rounded division and square root). With
+    ``x = z_q[0]``, ``y = z_q[1]``, ``|x|^2 = x.re*x.re + x.im*x.im``, ``a*b = (a.re*b.re -
+    a.im*b.im, a.re*b.im + a.im*b.re)`` and ``a*conj(b) = (a.re*b.re + a.im*b.im, a.im*b.re -
+    a.re*b.im)``, for ``k = 1 .. max_iterations``::
+
+        s00[q] = |x|^2;  s11[q] = |y|^2;  s01[q] = y*conj(x)
+        num0[p] = sum_q A[p][q]*x;  num1[p] = sum_q A[p][q]*y
+        h00[p] = sum_q W[p][q]*s00[q];  h11[p] = sum_q W[p][q]*s11[q]
+        h01[p] = sum_q (W[p][q]*s01[q].re, W[p][q]*s01[q].im)
+        det = h00*h11 - |h01|^2
+        det > 0:  c = num1*conj(h01);  e = num0*h01
+                  new0 = ((num0.re*h11 - c.re)/det, (num0.im*h11 - c.im)/det)
+                  new1 = ((num1.re*h00 - e.re)/det, (num1.im*h00 - e.im)/det)
+        else:     new = z_p                                     (a NaN det is not above 0)
+        k odd : z = new
+        k even: z = ((new.re + z.re)*0.5, (new.im + z.im)*0.5) for both elements,
+                d = sum_p (|z_p[0]-old_p[0]|^2 + |z_p[1]-old_p[1]|^2)
+                n = sum_p (|z_p[0]|^2 + |z_p[1]|^2)             over the inputs that have data
+                stop, converged, when d <= float32(tol*tol) * n
+
+    Every sum over q or p runs in the blocks of 32 of :class:`SolveGainsHost`. After the loop:
+
+    * Referencing. `reference` is an antenna, or -1. With ``R = [[a, b], [c, d]]`` its matrix
+      (``a, b = z_2r``; ``c, d = z_2r+1``), ``D = a*d - b*c`` and ``m = sqrt(|D|^2)``: if both
+      of its inputs have data and m is positive and finite, then ``e = (D.re/m, D.im/m)``,
+      ``B = [[a + e*conj(d), b - e*conj(c)], [c - e*conj(b), d + e*conj(a)]]``,
+      ``t = sqrt(sqrt(|B00*B11 - B01*B10|^2))``, ``U[i][j] = (B[i][j].re/t, B[i][j].im/t)`` and
+      every row becomes ``(x*conj(U00) + y*conj(U01), x*conj(U10) + y*conj(U11))``. U is the
+      unitary factor of R's polar decomposition, so the reference's matrix becomes Hermitian
+      and positive; the imaginary parts of its diagonal are set to +0. Otherwise status bit 2
+      is set and nothing is rotated. For an unpolarised source the data fix the matrices only
+      up to one common unitary factor on the right: this choice of U is a convention that the
+      data cannot check.
+    * With `corrections`, each antenna's matrix ``[[a, b], [c, d]]`` is replaced by its inverse:
+      ``D = a*d - b*c``, ``s = |D|^2``, ``i = (D.re/s, -D.im/s)`` and ``[[d*i, -(b*i)],
+      [-(c*i), a*i]]`` where ``s > 0`` and both inputs have data, else NaN in all four.
+    * Without corrections only the rows of inputs without data are NaN+NaNj.
+
+    ``status`` bits: 1 not converged, 2 no input has data, 4 not referenced, 8 in the last
+    iteration an input with data kept its row because ``det`` was not above 0.
+
+    Parameters
+    ----------
+    max_iterations, tol, mask
+        As for :class:`SolveGainsHost`
+    reference
+        -1 (none) or the antenna whose matrix is made Hermitian and positive, up to 63
+    corrections
+        ``True``: return the inverse matrices
+    """
+
+    MAX_ANTENNAS = SolveGainsHost.MAX_INPUTS // 2
+    DET_NOT_POSITIVE = 8
+
+    def __init__(self, max_iterations: int = 30, tol: float = 1e-5, reference: int = 0,
+                 mask: int = 0xFF, corrections: bool = False) -> None:  # fmt: skip
+        if isinstance(reference, (int, np.integer)) and not isinstance(reference, (bool, np.bool_)):
+            if not -1 <= reference < self.MAX_ANTENNAS:
+                raise ValueError(f"reference must be -1..{self.MAX_ANTENNAS - 1}")
+        super().__init__(max_iterations, tol, reference, mask, corrections)
+
+    @classmethod
+    def check_n_inputs(cls, n_inputs) -> int:
+        """`n_inputs` as an even int in 2..128 (``ValueError`` otherwise, ``TypeError`` for a
+        value that is not an integer)."""
+        if isinstance(n_inputs, (bool, np.bool_)) or not isinstance(n_inputs, (int, np.integer)):
+            raise TypeError(f"n_inputs {n_inputs!r} is not an integer")
+        if not 2 <= n_inputs <= cls.MAX_INPUTS or n_inputs % 2:
+            raise ValueError(f"n_inputs must be even and 2..{cls.MAX_INPUTS}")
+        return int(n_inputs)
+
+    def __call__(self, vis: np.ndarray, pairs: np.ndarray, weights: Optional[np.ndarray] = None,
+                 flags: Optional[np.ndarray] = None, initial: Optional[np.ndarray] = None):  # fmt: skip
+        """``(jones, iterations, status)``: complex64 (channels, n_inputs, 2), int32
+        (channels,) and uint8 (channels,), for complex64 `vis` (channels, baselines), int32
+        `pairs` (n_inputs, n_inputs), optional float32 `weights`, optional uint8 `flags` (both
+        channels, baselines) and optional complex64 `initial` (channels, n_inputs, 2).
+        ``ValueError``, naming the argument, for a wrong dtype, rank or shape (channels and
+        baselines at least 1, n_inputs even and 2..128) and for a `reference` that is not
+        below n_inputs / 2. No argument is modified."""
+        vis = _check_array("vis", vis, np.complex64, "(channels, baselines)",
+                           lambda s: len(s) == 2 and s[0] >= 1 and s[1] >= 1)  # fmt: skip
+        channels = vis.shape[0]
+        pairs = _check_array("pairs", pairs, np.int32,
+                             "(n_inputs, n_inputs), n_inputs even and 2..128",
+                             lambda s: len(s) == 2 and s[0] == s[1] and s[0] % 2 == 0
+                             and 2 <= s[0] <= self.MAX_INPUTS)  # fmt: skip
+        n = pairs.shape[0]
+        if weights is not None:
+            weights = _check_array("weights", weights, np.float32, "(channels, baselines)",
+                                   lambda s: s == vis.shape)  # fmt: skip
+        if flags is not None:
+            flags = _check_array("flags", flags, np.uint8, "(channels, baselines)",
+                                 lambda s: s == vis.shape)  # fmt: skip
+        if initial is not None:
+            initial = _check_array("initial", initial, np.complex64, "(channels, n_inputs, 2)",
+                                   lambda s: s == (channels, n, 2))  # fmt: skip
+        if self.reference >= n // 2:
+            raise ValueError(f"reference must be -1 or 0..n_inputs/2-1 = {n // 2 - 1}, "
+                             f"not {self.reference}")  # fmt: skip
+        # an entry within one antenna is no baseline (the lower triangle is never read)
+        index = np.arange(n) // 2
+        pairs = np.where(index[:, np.newaxis] == index[np.newaxis, :], np.int32(0), pairs)
+        jones = np.empty((channels, n, 2), np.complex64)
+        iterations = np.empty(channels, np.int32)
+        status = np.empty(channels, np.uint8)
+        for c0 in range(0, channels, self._CHUNK):
+            rows = slice(c0, min(c0 + self._CHUNK, channels))
+            jones[rows], iterations[rows], status[rows] = self._solve(
+                vis[rows], pairs, None if weights is None else weights[rows],
+                None if flags is None else flags[rows],
+                None if initial is None else initial[rows])  # fmt: skip
+        return jones, iterations, status
+
+    @staticmethod
+    def _mul(a, b):
+        """``a*b`` of the class docstring on (re, im) pairs."""
+        return a[0] * b[0] - a[1] * b[1], a[0] * b[1] + a[1] * b[0]
+
+    @staticmethod
+    def _mul_conj(a, b):
+        """``a*conj(b)`` of the class docstring on (re, im) pairs."""
+        return a[0] * b[0] + a[1] * b[1], a[1] * b[0] - a[0] * b[1]
+
+    @staticmethod
+    def _norm2(a):
+        return a[0] * a[0] + a[1] * a[1]
+
+    def _solve(self, vis, pairs, weights, flags, initial):
+        channels = vis.shape[0]
+        n = pairs.shape[0]
+        f32 = np.float32
+        half, zero, one, nan = f32(0.5), f32(0), f32(1), f32(np.nan)
+        bsum, mul, mul_conj, norm2 = self._block_sum, self._mul, self._mul_conj, self._norm2
+        with np.errstate(all="ignore"):
+            a_re, a_im, w = self._matrix(vis, pairs, weights, flags)
+            has = (w > 0).any(axis=2)
+            # z[e][part]: element e of every row, real and imaginary parts apart
+            if initial is None:
+                even = (np.arange(n) % 2 == 0)[np.newaxis, :].repeat(channels, axis=0)
+                z = [[even.astype(f32), np.zeros((channels, n), f32)],
+                     [(~even).astype(f32), np.zeros((channels, n), f32)]]  # fmt: skip
+            else:
+                z = [[np.array(initial[:, :, e].real), np.array(initial[:, :, e].imag)]
+                     for e in range(2)]  # fmt: skip
+            iterations = np.zeros(channels, np.int32)
+            converged = np.zeros(channels, bool)
+            stuck = np.zeros(channels, bool)
+            for k in range(1, self.max_iterations + 1):
+                act = np.flatnonzero(~converged)
+                if not act.size:
+                    break
+                x = (z[0][0][act], z[0][1][act])
+                y = (z[1][0][act], z[1][1][act])
+                s00, s11, s01 = norm2(x), norm2(y), mul_conj(y, x)
+                a = (a_re[act], a_im[act])
+                wa = w[act]
+
+                def over_q(v):
+                    return v[:, np.newaxis, :]
+
+                num0 = tuple(bsum(t) for t in mul(a, (over_q(x[0]), over_q(x[1]))))
+                num1 = tuple(bsum(t) for t in mul(a, (over_q(y[0]), over_q(y[1]))))
+                h00, h11 = bsum(wa * over_q(s00)), bsum(wa * over_q(s11))
+                h01 = (bsum(wa * over_q(s01[0])), bsum(wa * over_q(s01[1])))
+                det = h00 * h11 - norm2(h01)
+                pos = det > 0
+                safe = np.where(pos, det, one)  # (no 0 / 0 where the quotient is not used)
+                c, e = mul_conj(num1, h01), mul(num0, h01)
+                new = [[np.where(pos, (num0[i] * h11 - c[i]) / safe, x[i]) for i in range(2)],
+                       [np.where(pos, (num1[i] * h00 - e[i]) / safe, y[i]) for i in range(2)]]
+                stuck[act] = (has[act] & ~pos).any(axis=1)
+                if k % 2 == 0:
+                    old = (x, y)
+                    new = [[(new[e][i] + old[e][i]) * half for i in range(2)] for e in range(2)]
+                    diff = [(new[e][0] - old[e][0], new[e][1] - old[e][1]) for e in range(2)]
+                    d = bsum(np.where(has[act], norm2(diff[0]) + norm2(diff[1]), zero))
+                    norm = bsum(np.where(has[act], norm2(new[0]) + norm2(new[1]), zero))
+                    converged[act] = d <= self.tol2 * norm
+                for e in range(2):
+                    for i in range(2):
+                        z[e][i][act] = new[e][i]
+                iterations[act] = k
+            status = np.where(converged, 0, self.NOT_CONVERGED).astype(np.uint8)
+            status[~has.any(axis=1)] |= np.uint8(self.NO_DATA)
+            status[stuck] |= np.uint8(self.DET_NOT_POSITIVE)
+            x, y = (z[0][0], z[0][1]), (z[1][0], z[1][1])
+            # referencing
+            referenced = np.zeros(channels, bool)
+            if self.reference >= 0:
+                r0, r1 = 2 * self.reference, 2 * self.reference + 1
+
+                def at(v, p):
+                    return v[0][:, p], v[1][:, p]
+
+                ra, rb, rc, rd = at(x, r0), at(y, r0), at(x, r1), at(y, r1)
+                ad, bc = mul(ra, rd), mul(rb, rc)
+                big_d = (ad[0] - bc[0], ad[1] - bc[1])
+                m = np.sqrt(norm2(big_d))
+                referenced = has[:, r0] & has[:, r1] & (m > 0) & np.isfinite(m)
+                safe = np.where(referenced, m, one)
+                e = (big_d[0] / safe, big_d[1] / safe)
+                ed, ec, eb, ea = mul_conj(e, rd), mul_conj(e, rc), mul_conj(e, rb), mul_conj(e, ra)
+                b00 = (ra[0] + ed[0], ra[1] + ed[1])
+                b01 = (rb[0] - ec[0], rb[1] - ec[1])
+                b10 = (rc[0] - eb[0], rc[1] - eb[1])
+                b11 = (rd[0] + ea[0], rd[1] + ea[1])
+                p00, p01 = mul(b00, b11), mul(b01, b10)
+                t = np.sqrt(np.sqrt(norm2((p00[0] - p01[0], p00[1] - p01[1]))))
+                t = np.where(referenced, t, one)
+                u = [tuple((part / t)[:, np.newaxis] for part in b) for b in (b00, b01, b10, b11)]
+                rows = referenced[:, np.newaxis]
+                turned = []
+                for u0, u1 in ((u[0], u[1]), (u[2], u[3])):
+                    first, second = mul_conj(x, u0), mul_conj(y, u1)
+                    turned.append((first[0] + second[0], first[1] + second[1]))
+                x = tuple(np.where(rows, turned[0][i], x[i]) for i in range(2))
+                y = tuple(np.where(rows, turned[1][i], y[i]) for i in range(2))
+                x[1][:, r0] = np.where(referenced, zero, x[1][:, r0])
+                y[1][:, r1] = np.where(referenced, zero, y[1][:, r1])
+            status[~referenced] |= np.uint8(self.NOT_REFERENCED)
+            if self.corrections:
+                ja, jb = (x[0][:, 0::2], x[1][:, 0::2]), (y[0][:, 0::2], y[1][:, 0::2])
+                jc, jd = (x[0][:, 1::2], x[1][:, 1::2]), (y[0][:, 1::2], y[1][:, 1::2])
+                ad, bc = mul(ja, jd), mul(jb, jc)
+                big_d = (ad[0] - bc[0], ad[1] - bc[1])
+                s = norm2(big_d)
+                pos = (s > 0) & has[:, 0::2] & has[:, 1::2]
+                safe = np.where(pos, s, one)
+                inv = (big_d[0] / safe, -big_d[1] / safe)
+                di, bi, ci, ai = mul(jd, inv), mul(jb, inv), mul(jc, inv), mul(ja, inv)
+                x = tuple(np.empty((channels, n), f32) for _ in range(2))
+                y = tuple(np.empty((channels, n), f32) for _ in range(2))
+                for i in range(2):
+                    x[i][:, 0::2] = np.where(pos, di[i], nan)
+                    y[i][:, 0::2] = np.where(pos, -bi[i], nan)
+                    x[i][:, 1::2] = np.where(pos, -ci[i], nan)
+                    y[i][:, 1::2] = np.where(pos, ai[i], nan)
+            else:
+                x = tuple(np.where(has, part, nan) for part in x)
+                y = tuple(np.where(has, part, nan) for part in y)
+            jones = np.empty((channels, n, 2), np.complex64)
+            jones.real[:, :, 0], jones.imag[:, :, 0] = x
+            jones.real[:, :, 1], jones.imag[:, :, 1] = y
+            assert all(part.dtype == f32 for part in x + y)
+        return jones, iterations, status
+
+
 class PredictHost:
     """Model visibilities of point sources and, optionally, the data divided by them: the step
     in front of :class:`SolveGainsHost` for a calibrator that is not a unit source at the phase

@@ -679,6 +679,180 @@ class SolveGainsHostFromDevice:
         return out[0], out[1], out[2]
 
 
+class SolveJonesTemplate(_native_op.NativeTemplate):
+    """The leakage solve beside :class:`SolveGainsTemplate`: per channel, one 2x2 Jones matrix
+    per dual-feed antenna, solved with the full-polarisation StEFCal step from the ``vis``,
+    ``weights`` and ``flags`` that :class:`.device.Finalise` (or :class:`Predict` with
+    ``divide``) leaves, cross-hand baselines included, in one kernel launch with one workgroup
+    per channel; see :class:`host.SolveJonesHost` for every step.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    weights
+        ``True``: there is a `weights` slot (every weight is 1 otherwise)
+    flags
+        ``True``: there is a `flags` slot
+    initial
+        ``True``: there is an `initial` slot with the matrices to start from (the identity
+        otherwise)
+    max_iterations, tol, reference, mask, corrections
+        As for :class:`host.SolveJonesHost` (same errors)
+    tuning
+        The kernel picks its launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.SolveJonesHost
+    KERNEL = "ksp_solve_jones"
+
+    def __init__(self, context: AbstractContext, weights: bool = True, flags: bool = True,
+                 initial: bool = False, max_iterations: int = 30, tol: float = 1e-5,
+                 reference: int = 0, mask: int = 0xFF, corrections: bool = False,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        self.weights = bool(weights)
+        self.flags = bool(flags)
+        self.initial = bool(initial)
+        checked = host.SolveJonesHost(max_iterations, tol, reference, mask, corrections)
+        self.max_iterations = checked.max_iterations
+        self.tol = checked.tol
+        self.tol2 = checked.tol2
+        self.reference = checked.reference
+        self.mask = checked.mask
+        self.corrections = checked.corrections
+        self._setup(context, tuning)
+
+
+class SolveJones(_native_op.NativeOperation):
+    """Concrete :class:`SolveJonesTemplate` (``ValueError`` if `channels` or `baselines` is
+    below 1, `n_inputs` odd or outside 2..128, or the template's `reference` not below
+    ``n_inputs / 2``).
+
+    .. rubric:: Slots
+
+    **vis** : channels x baselines, complex64
+    **weights** : channels x baselines, float32 (only with ``weights``)
+    **flags** : channels x baselines, uint8 (only with ``flags``)
+    **pairs** : n_inputs x n_inputs, int32 (:meth:`host.SolveGainsHost.pair_table`)
+    **initial** : channels x n_inputs x 2, complex64 (only with ``initial``)
+    **jones** : channels x n_inputs x 2, complex64
+    **iterations** : channels, int32
+    **status** : channels, uint8
+
+    Every padded dimension is an object of its own, so ``vis``, ``weights`` and ``flags`` can
+    be compounded with :class:`.device.Finalise`'s or :class:`Predict`'s outputs, each taking
+    the other's padding; the last axis of ``initial`` and ``jones`` is never padded. Binding
+    one buffer to ``initial`` and ``jones`` refines the matrices in place.
+    """
+
+    def __init__(self, template: SolveJonesTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int, n_inputs: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        if channels < 1 or baselines < 1:
+            raise ValueError("channels and baselines must be at least 1")
+        self.n_inputs = host.SolveJonesHost.check_n_inputs(n_inputs)
+        if template.reference >= n_inputs // 2:
+            raise ValueError(f"reference must be -1 or 0..n_inputs/2-1 = {n_inputs // 2 - 1}, "
+                             f"not {template.reference}")  # fmt: skip
+
+        def samples(dtype) -> accel.IOSlot:
+            return accel.IOSlot((channels, accel.Dimension(baselines)), dtype)
+
+        def per_input() -> accel.IOSlot:
+            return accel.IOSlot((channels, accel.Dimension(n_inputs),
+                                 accel.Dimension(2, exact=True)), np.complex64)  # fmt: skip
+
+        self.slots["vis"] = samples(np.complex64)
+        if template.weights:
+            self.slots["weights"] = samples(np.float32)
+        if template.flags:
+            self.slots["flags"] = samples(np.uint8)
+        self.slots["pairs"] = accel.IOSlot(
+            (accel.Dimension(n_inputs), accel.Dimension(n_inputs)), np.int32)  # fmt: skip
+        if template.initial:
+            self.slots["initial"] = per_input()
+        self.slots["jones"] = per_input()
+        self.slots["iterations"] = accel.IOSlot((accel.Dimension(channels),), np.int32)
+        self.slots["status"] = accel.IOSlot((accel.Dimension(channels),), np.uint8)
+
+    def _run(self) -> None:
+        template = self.template
+        vis, pairs, jones = self.buffer("vis"), self.buffer("pairs"), self.buffer("jones")
+        weights = self.buffer("weights") if template.weights else None
+        flags = self.buffer("flags") if template.flags else None
+        initial = self.buffer("initial") if template.initial else None
+        self._launch(
+            vis.buffer,
+            _native_op.pointer(weights),
+            _native_op.pointer(flags),
+            pairs.buffer,
+            _native_op.pointer(initial),
+            jones.buffer,
+            self.buffer("iterations").buffer,
+            self.buffer("status").buffer,
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(self.n_inputs),
+            np.int32(vis.padded_shape[1]),
+            _native_op.stride(weights),
+            _native_op.stride(flags),
+            np.int32(pairs.padded_shape[1]),
+            _native_op.stride(initial),
+            np.int32(jones.padded_shape[1]),
+            np.int32(template.max_iterations),
+            np.float32(template.tol2),
+            np.int32(template.reference),
+            np.int32(template.mask),
+            np.int32(template.corrections),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        template = self.template
+        return self._parameters(
+            weights=template.weights, flags=template.flags, initial=template.initial,
+            max_iterations=template.max_iterations, tol=template.tol,
+            reference=template.reference, mask=template.mask, corrections=template.corrections,
+            n_inputs=self.n_inputs)  # fmt: skip
+
+
+SolveJonesTemplate.operation_class = SolveJones
+
+
+class SolveJonesHostFromDevice:
+    """Make a :class:`SolveJonesTemplate` callable like :class:`host.SolveJonesHost`, but with
+    the ``inputs`` (baselines x 2) that :class:`ApplyGainsHostFromDevice` takes instead of the
+    table, which it builds (:meth:`host.SolveGainsHost.pair_table`): ``(vis, inputs, n_inputs,
+    weights=None, flags=None, initial=None)`` in, ``(jones, iterations, status)`` out; allocates
+    on every call. ``TypeError`` unless `weights`, `flags` and `initial` are each given exactly
+    when the template has them."""
+
+    def __init__(self, template: SolveJonesTemplate, command_queue: AbstractCommandQueue) -> None:
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, vis: np.ndarray, inputs: np.ndarray, n_inputs: int,
+                 weights: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None,
+                 initial: Optional[np.ndarray] = None
+                 ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:  # fmt: skip
+        template = self.template
+        _native_op.check_optional(weights, template.weights, "weights")
+        _native_op.check_optional(flags, template.flags, "flags")
+        _native_op.check_optional(initial, template.initial, "initial")
+        channels, baselines = vis.shape
+        if np.shape(inputs) != (baselines, 2):
+            raise ValueError(f"inputs must have shape (baselines, 2) = ({baselines}, 2), "
+                             f"not {np.shape(inputs)}")  # fmt: skip
+        pairs = host.SolveJonesHost.pair_table(inputs, n_inputs)
+        fn = template.instantiate(self.command_queue, channels, baselines, n_inputs)
+        given = {"vis": vis, "pairs": pairs, "weights": weights, "flags": flags,
+                 "initial": initial}  # fmt: skip
+        out = _native_op.run_once(fn, self.command_queue, given,
+                                  ["jones", "iterations", "status"])  # fmt: skip
+        return out[0], out[1], out[2]
+
+
 class PredictTemplate(_native_op.NativeTemplate):
     """The step in front of :class:`SolveGainsTemplate` for a calibrator that is not a unit
     source at the phase centre: the model visibilities of up to 64 point sources evaluated per
