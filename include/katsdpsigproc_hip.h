@@ -158,7 +158,8 @@ int ksp_background_median_filter_geometry(int channels, int baselines, int width
                                           int *seg_len, int *n_segs);
 
 /* madnz_t (reference: rfi/madnz_t.mako:72-87; launch rfi/device.py:594-607).
- * in: [B][stride] float32; noise[b] = float32(1.4826 * median(|x| : x != 0)).
+ * in: [B][stride] float32; noise[b] = float32(1.4826 * median(|x| : |x| > 0)): zeros and
+ * NaN take no part, +-inf do; NaN if nothing is left.
  * channels 1..262144; more is rejected before any device call. */
 int ksp_madnz_t(int device, void *stream, const float *in, float *noise, int channels,
                 int baselines, int stride);

@@ -16,9 +16,12 @@
 // selected one hold the rest. The rounding is madnz_t_kernel's: float32 (a + b) * 0.5,
 // then 1.4826 in float64, rounded once; no non-zero value gives NaN.
 //
-// NaN input: |x| is ordered by its magnitude bit pattern like every other value, so a
-// NaN counts as a non-zero value above +inf; the result is NaN when the median lands on
-// one. (The oracle does not pin this.)
+// NaN input: a NaN deviation takes no part, exactly like a zero (the definition is
+// |x| > 0, which a NaN fails). Pass 1 counts the patterns 1 .. 0x7f800000 (+inf) only, so
+// the count and the rank are those of the values that do take part. NaN patterns lie above
+// every such value: where passes 2 and 3 count some (the median is +inf), they fill bins
+// behind the one that holds the rank and change nothing. A row of nothing but NaN and zeros
+// gives NaN. (tests/test_gpu_nan_deviations.py pins this against rfi.host.NoiseEstMADHost.)
 //
 // Rows of up to MADL_STAGE_MAX channels are kept in LDS as patterns by pass 1 (144 KiB
 // at most, one workgroup per CU), so HBM is read once. Longer rows are read from global
@@ -64,7 +67,7 @@ __device__ __forceinline__ uint4 madl_load4(const float *row, int c, int channel
     return q;
 }
 
-// One histogram pass. PASS 1: bins = bits 30..20 of every non-zero pattern (and, when
+// One histogram pass. PASS 1: bins = bits 30..20 of every pattern that is neither 0 nor a NaN's (and, when
 // STAGED, the patterns are stored to `stage`); PASS 2: bits 19..9 of those whose top 11
 // bits are `prefix`; PASS 3: bits 8..0 of those whose top 22 bits are `prefix`, returning
 // this thread's largest non-zero pattern below prefix << 9 (0 if none).
@@ -78,8 +81,9 @@ __device__ __forceinline__ unsigned madl_pass(const float *row, unsigned *stage,
     const unsigned lim = PASS == 3 ? prefix << 9 : 0u;
     unsigned best = 0;
     auto one = [&](unsigned p) {
-        // PASS 1: p >> 31 == 0 leaves out MADL_NONE
-        ksp_hist_count(hist, (p >> BSHIFT) & BMASK, p != 0 && (p >> MSHIFT) == prefix);
+        // PASS 1: 1 <= p <= 0x7f800000 leaves out zeros, NaN and MADL_NONE
+        const bool counts = PASS == 1 ? p - 1u < 0x7f800000u : (p != 0 && (p >> MSHIFT) == prefix);
+        ksp_hist_count(hist, (p >> BSHIFT) & BMASK, counts);
         if (PASS == 3) best = max(best, (p != 0 && p < lim) ? p : 0u);
     };
     auto quad = [&](uint4 q) {

@@ -13,6 +13,14 @@
 // Rows of 16385..262144 channels take madnz_t_long_kernel (madnz_long.h): one
 // 1024-thread workgroup per baseline, radix select over three histogram passes.
 //
+// NaN input: the definition takes |x| > 0 (reference rfi/host.py:161-162), which a NaN fails
+// like a zero: a NaN deviation takes no part. By its magnitude pattern a NaN sorts above
+// +inf, behind every value that counts, so a kernel either loads it as +0 and counts it with
+// the zeros (madnz_t_kernel: madnz_pattern below) or leaves it where it is, counts the NaN
+// and takes the rank among the rest: with z zeros and k NaN among n values the median of the
+// others has rank (n + z - k) / 2 in the whole row (wave_median_nonzero, madnz_kernel;
+// madnz_long.h keeps both zeros and NaN out of its first histogram).
+//
 // Numerics (reference rfi/host.py:157-163 on float32 input): numpy.median stays in
 // float32 -- even count -> float32(a + b) * 0.5 -- and the 1.4826 scale is applied
 // in float64; the float32 output is that float64 product rounded once.
@@ -21,6 +29,14 @@
 #include "rank.h"
 
 #define KSP_MAD_NORMAL 1.4826
+
+// The 31-bit pattern of |x|, 0 for a NaN (any pattern above +inf's): a NaN deviation takes no
+// part in the median, exactly like a zero.
+__device__ __forceinline__ unsigned madnz_pattern(unsigned bits)
+{
+    const unsigned p = bits & 0x7fffffffu;
+    return p > 0x7f800000u ? 0u : p;
+}
 
 #include "madnz_long.h"
 
@@ -37,7 +53,9 @@ __global__ __launch_bounds__(KSP_RANK_THREADS) void madnz_t_kernel(const float *
 #pragma unroll
     for (int i = 0; i < VT; i++) {
         const int c = i * KSP_RANK_THREADS + t;
-        v[i] = (c < channels) ? fabsf(row[c]) : __builtin_nanf("");
+        // (padding is NaN, as rank.h wants it; a NaN in the data is a zero)
+        v[i] = (c < channels) ? __uint_as_float(madnz_pattern(__float_as_uint(row[c])))
+                              : __builtin_nanf("");
     }
     const float med = block_median_non_zero(v, channels, &scratch);
     if (t == 0) noise[bl] = (float)((double)med * KSP_MAD_NORMAL);
@@ -52,8 +70,8 @@ __global__ __launch_bounds__(KSP_RANK_THREADS) void madnz_t_kernel(const float *
 // -- two bits per step, no LDS, no barriers -- instead of a compare per value and a
 // workgroup reduction per bit.
 // The search itself: u[64] are the lane's 64 |x| patterns (0x7fffffff for channels that
-// do not exist); returns the float32 median of the non-zero values of the row (NaN if
-// there are none), identical in every lane.
+// do not exist); returns the float32 median of the values of the row that are neither zero
+// nor NaN (NaN if there are none), identical in every lane.
 __device__ __forceinline__ float wave_median_nonzero(const unsigned (&u)[64], int channels)
 {
     // inverted bit planes: hi[b] / hi[16 + b] = bit 16 + b of the even / odd values
@@ -69,22 +87,37 @@ __device__ __forceinline__ float wave_median_nonzero(const unsigned (&u)[64], in
     auto plane = [&](int bit, int half) -> unsigned {
         return bit >= 16 ? hi[16 * half + bit - 16] : lo[16 * half + bit];
     };
-    // zeros: every one of the 31 bits clear
-    unsigned z0 = lo[0], z1 = lo[16];
+    // mantissa (bits 0..22) all clear; exponent (bits 23..30) all clear / not all set
+    unsigned m0 = lo[0], m1 = lo[16];
 #pragma unroll
     for (int b = 1; b < 16; b++) {
-        z0 &= lo[b];
-        z1 &= lo[16 + b];
+        m0 &= lo[b];
+        m1 &= lo[16 + b];
     }
 #pragma unroll
-    for (int b = 0; b < 15; b++) {
-        z0 &= hi[b];
-        z1 &= hi[16 + b];
+    for (int b = 0; b < 7; b++) {
+        m0 &= hi[b];
+        m1 &= hi[16 + b];
     }
-    const int zeros = ksp_wave_sum_dpp(__popc(z0) + __popc(z1));
-    // zeros sort first, so the median of the non-zero values has rank
-    // (channels + zeros) / 2 in the whole row (reference rank.mako:261-266)
-    const int rank2 = channels + zeros;
+    unsigned e0 = hi[7], e1 = hi[23], f0 = hi[7], f1 = hi[23];
+#pragma unroll
+    for (int b = 8; b < 15; b++) {
+        e0 &= hi[b];
+        e1 &= hi[16 + b];
+        f0 |= hi[b];
+        f1 |= hi[16 + b];
+    }
+    // zeros: every one of the 31 bits clear. NaN: exponent all set, mantissa not clear; the
+    // 64 * 64 - channels patterns of channels that do not exist are among them. Both counts
+    // (at most 4096) share one wave reduction.
+    const int packed = ksp_wave_sum_dpp(__popc(m0 & e0) + __popc(m1 & e1) +
+                                        ((__popc(~(f0 | m0)) + __popc(~(f1 | m1))) << 16));
+    const int zeros = packed & 0xffff;
+    const int nans = (packed >> 16) - (64 * 64 - channels);
+    // zeros sort first and NaN last, so the median of the values that count (non-zero, not
+    // NaN) has rank (channels + zeros - nans) / 2 in the whole row (reference
+    // rank.mako:261-266 for the zeros)
+    const int rank2 = channels + zeros - nans;
     const int rank = rank2 / 2;
     PlaneSearch<decltype(plane)> search(rank, plane);
     // (one bit per step: measured faster than two-bit steps here as in the fused kernel)
@@ -133,7 +166,7 @@ __device__ __forceinline__ float wave_median_nonzero(const unsigned (&u)[64], in
         }
         result = __fmul_rn(__fadd_rn(result, prev), 0.5f);
     }
-    if (zeros == channels) result = __builtin_nanf("");  // numpy: median of nothing
+    if (zeros + nans == channels) result = __builtin_nanf("");  // numpy: median of nothing
     return result;
 }
 
@@ -307,9 +340,13 @@ __global__ __launch_bounds__(64 * MADNZ_PHASES) void madnz_kernel(const float *_
         return c;
     };
 
-    // number of zeros = keys below the pattern of the smallest positive float
+    // number of zeros = keys below the pattern of the smallest positive float; number of NaN =
+    // keys not below the pattern of the smallest one. NaN sort last, so the median of the
+    // values that count has rank (channels + zeros - nans) / 2 in the whole column, and no
+    // pivot of the search reaches them.
     const int zeros = count_below(1u, nullptr);
-    const int rank2 = channels + zeros;
+    const int nans = channels - count_below(0x7f800001u, nullptr);
+    const int rank2 = channels + zeros - nans;
     const int rank = rank2 / 2;
     unsigned cur = 0;
     for (int bit = 30; bit >= 0; bit--) {
@@ -324,7 +361,7 @@ __global__ __launch_bounds__(64 * MADNZ_PHASES) void madnz_kernel(const float *_
         const float prev = (c == rank) ? below : result;
         result = __fmul_rn(__fadd_rn(result, prev), 0.5f);
     }
-    if (zeros == channels) result = __builtin_nanf("");
+    if (zeros + nans == channels) result = __builtin_nanf("");
     if (phase == 0 && active) noise[b] = (float)((double)result * KSP_MAD_NORMAL);
 }
 

@@ -265,6 +265,23 @@ def nonfinite_amp_case(channels=1024, seed=22):
     return amp, flags
 
 
+def nonfinite_amp_nan_case(channels=1024, seed=22):
+    """nonfinite_amp_case with NaN amplitudes in place of and next to the +-inf of columns
+    0-2 (the background leaves a NaN out of every window, and its own deviation is 0):
+    0 NaN in place of the +inf and on either side of the -inf; 1 NaN at both ends of and
+    inside the long run of -inf, in the middle of the short one and behind it; 2 NaN in place
+    of the +inf between the negative amplitudes and in front of the -inf. Columns 3 and 4 and
+    the input flags are nonfinite_amp_case's."""
+    amp, flags = nonfinite_amp_case(channels, seed)
+    amp[100, 0] = np.nan
+    amp[[399, 401], 0] = np.nan
+    amp[[199, 200, 210, 219, 220], 1] = np.nan
+    amp[[601, 603], 1] = np.nan
+    amp[301, 2] = np.nan
+    amp[699, 2] = np.nan
+    return amp, flags
+
+
 def nonfinite_mad_case(channels, seed=23):
     """float32 deviations [channels][6] for the MAD noise estimate: 0 a few +-inf among unit
     noise; 1 more than half of them inf; 2 exactly half inf (the even-count midpoint is
