@@ -653,6 +653,50 @@ int ksp_solve_jones(int device, void *stream, const void *vis, const float *weig
                     int pairs_stride, int initial_stride, int jones_stride, int max_iterations,
                     float tol2, int reference, int mask, int corrections);
 
+/* apply_jones: per-antenna 2x2 Jones corrections applied to visibilities, weights and flags,
+ * C_a V_ab C_b^H on the four products of every antenna pair, in one launch (no reference
+ * counterpart; bit for bit what rfi/host.py ApplyJonesHost computes, whose docstring states
+ * every step and the order of the operations inside it; every float step is one float32
+ * operation, rounded once, a multiply then an add, never an fma; correctly rounded division).
+ * vis, out_vis: complex64 [channels][stride]; weights, out_weights: float32; flags, out_flags:
+ * uint8; jones: complex64 [channels][jones_stride][2] as ksp_solve_jones writes it (with
+ * corrections != 0, the matrices that multiply), of which n_inputs rows per channel are data:
+ * row 2a + i is row i of antenna a's matrix C_a. jones_stride counts rows of two complex64 (16
+ * bytes); the other strides count elements. quad_antennas: int32 [n_quads][2], contiguous: the
+ * antennas (a, b) of every quad; quads: int32 [n_quads][4], contiguous: its entries (t00, t01,
+ * t10, t11), where t at (m, n) follows the rules of ksp_solve_gains' pairs: t > 0 is baseline
+ * t - 1 listed as (2a+m, 2b+n), t < 0 is baseline -t - 1 listed the other way round, whose
+ * imaginary part is negated on load and again on store, and 0 or |t| > baselines (any int32,
+ * INT32_MIN included) is absent and forms no address. With a == b an absent (1,0) beside a
+ * present (0,1) reads as the conjugate of that sample, with its weight and flags, and the
+ * other way round. Per channel c and quad:
+ *   complete = 0 <= a, b < n_inputs / 2 and all four sources are there (a stand-in counts);
+ *   ok = complete and none of the 16 floats of rows 2a, 2a+1, 2b, 2b+1 of jones[c] is NaN;
+ *   T[i][n] = C_a[i][0] S[0][n] + C_a[i][1] S[1][n];
+ *   O[i][k] = T[i][0] conj(C_b[k][0]) + T[i][1] conj(C_b[k][1]);
+ *   u[i][n] = |C_a[i][0]|^2 / w[0][n] + |C_a[i][1]|^2 / w[1][n]   (1 / w first, then the product);
+ *   var[i][k] = u[i][0] |C_b[k][0]|^2 + u[i][1] |C_b[k][1]|^2;
+ *   for every entry (i, k) that is present itself, at its baseline j:
+ *   out_vis[c][j] = ok ? O[i][k] : vis[c][j];
+ *   out_weights[c][j] = ok and every w > 0 and var[i][k] > 0 ? 1 / var[i][k] : 0;
+ *   out_flags[c][j] = OR of the flags of the present sources | (ok ? 0 : flag_value).
+ * A baseline that no present entry names is neither read nor written. A baseline named by two
+ * present entries is the caller's breach: those baselines are undefined, nothing else is. An
+ * antenna outside 0 .. n_inputs / 2 - 1 (any int32) forms no address: its quad is not complete.
+ * weights and out_weights are both NULL or both given, and so are flags and out_flags. An
+ * output may be its input (the same pointer with the same stride: in place); otherwise it must
+ * share no byte with it. jones and the two tables must not overlap any output; jones needs the
+ * alignment of a complex64 only. n_inputs is even and 2..2048, n_quads, channels and baselines
+ * at least 1, flag_value 1..255. Elements between baselines (or n_inputs) and a stride are
+ * neither read nor written. One kernel launch, no workspace, no atomics. Every argument is
+ * checked before any device call. */
+int ksp_apply_jones(int device, void *stream, const void *vis, const float *weights,
+                    const uint8_t *flags, const void *jones, const int32_t *quad_antennas,
+                    const int32_t *quads, void *out_vis, float *out_weights, uint8_t *out_flags,
+                    int channels, int baselines, int n_inputs, int n_quads, int vis_stride,
+                    int weights_stride, int flags_stride, int jones_stride, int out_vis_stride,
+                    int out_weights_stride, int out_flags_stride, int flag_value);
+
 /* predict: model visibilities of up to 64 point sources and, optionally, the data divided by
  * them, in one launch: the step in front of ksp_solve_gains for a calibrator that is not a unit
  * source at the phase centre (no reference counterpart; bit for bit what rfi/host.py

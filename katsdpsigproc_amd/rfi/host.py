@@ -1251,6 +1251,241 @@ class SolveJonesHost(SolveGainsHost):
         return jones, iterations, status
 
 
+class ApplyJonesHost:
+    """Per-antenna 2x2 Jones corrections applied to averaged visibilities, ``C_a V_ab C_b^H``
+    on the four products of every antenna pair, with the weights propagated and the samples
+    without a correction flagged: what :class:`ApplyGainsHost` does for one complex number per
+    input, for the matrices that :class:`SolveJonesHost` leaves with ``corrections=True``. No
+    reference counterpart; this class is the definition that the device operation
+    (:class:`.ingest.ApplyJonesTemplate`) matches bit for bit.
+
+    ``jones`` is complex64 (channels, n_inputs, 2) as :class:`SolveJonesHost` writes it: row
+    ``2a + i`` is row ``i`` of antenna ``a``'s matrix ``C_a``; ``n_inputs`` is even, 2..2048.
+    The unit of work is a *quad*, the four products of one antenna pair: ``quad_antennas[q]``
+    is ``(a, b)`` and ``quads[q]`` is ``(t00, t01, t10, t11)``, where the entry ``t`` at
+    ``(m, n)`` is in the convention of ``pairs`` (:class:`SolveGainsHost`): ``t > 0`` is
+    baseline ``t - 1`` listed as ``(2a+m, 2b+n)``, ``t < 0`` is baseline ``-t - 1`` listed the
+    other way round, whose imaginary part is negated on load and again on store, and ``0`` or
+    ``|t| > baselines`` (any int32) is absent and forms no address. In a quad with ``a == b``
+    (a dish's own products) an absent ``(1, 0)`` beside a present ``(0, 1)`` reads as the
+    conjugate of that sample with its ``w`` and ``f``, and the other way round; nothing is
+    stored for an absent entry. :meth:`quad_table` builds both arrays.
+
+    Per channel ``c`` and quad, every float step is one float32 operation, rounded once (a
+    multiply, then an add, never an fma; real and imaginary parts apart; correctly rounded
+    division), sums added in the order written, with ``x*y = (x.re*y.re - x.im*y.im,
+    x.re*y.im + x.im*y.re)`` and ``x*conj(y) = (x.re*y.re + x.im*y.im, x.im*y.re -
+    x.re*y.im)``::
+
+        complete = 0 <= a < n_ant and 0 <= b < n_ant and all four sources present
+                   (a stand-in counts)
+        ok       = complete and none of the 16 floats of rows 2a, 2a+1, 2b, 2b+1 of jones[c]
+                   is NaN            (jones is not looked up unless both antennas are in range)
+        S[m][n]  = source sample (re, t<0 ? -im : im);  w[m][n] (1 without weights);  f[m][n]
+        T[i][n]  = C_a[i][0]*S[0][n] + C_a[i][1]*S[1][n]
+        O[i][k]  = T[i][0]*conj(C_b[k][0]) + T[i][1]*conj(C_b[k][1])
+        all_w    = every w[m][n] > 0                                     (a NaN is not)
+        r[m][n]  = 1 / w[m][n];   al[i][m] = |C_a[i][m]|^2;   be[k][n] = |C_b[k][n]|^2
+        u[i][n]  = al[i][0]*r[0][n] + al[i][1]*r[1][n]
+        var[i][k]= u[i][0]*be[k][0] + u[i][1]*be[k][1]
+        F        = OR of f over the present sources
+        for every entry (i, k) that is present in `quads` itself, at baseline j:
+          out_vis[c][j]     = ok ? (O.re, t<0 ? -O.im : O.im) : vis[c][j]   (the input's bits)
+          out_weights[c][j] = ok and all_w and var[i][k] > 0 ? 1/var[i][k] : 0
+          out_flags[c][j]   = F | (ok ? 0 : flag_value)
+
+    ``var[i][k]`` is the variance of ``O[i][k]`` for independent sources of variance ``1/w``.
+    What follows from it:
+
+    * A flag or a missing weight on one product reaches all four: a polarimetric correction
+      needs the whole coherency matrix.
+    * An incomplete quad or a NaN matrix passes its visibilities through bit for bit, with
+      weight 0 and `flag_value`.
+    * Infinities, denormals and NaN samples go as IEEE gives them.
+    * An autocorrelation does not stay exactly real.
+    * A baseline in no quad is not written at all: here its outputs are the inputs; on the
+      device it keeps its values in place, and out of place its output elements are untouched.
+
+    Parameters
+    ----------
+    flag_value
+        Bits set in ``out_flags`` of a sample without a correction, 1..255
+        (:func:`check_flag_byte`)
+    """
+
+    MAX_INPUTS = 2048
+
+    def __init__(self, flag_value: int = 128) -> None:
+        self.flag_value = check_flag_byte("flag_value", flag_value)
+
+    @classmethod
+    def check_n_inputs(cls, n_inputs) -> int:
+        """`n_inputs` as an even int in 2..2048 (``ValueError`` otherwise, ``TypeError`` for a
+        value that is not an integer)."""
+        if isinstance(n_inputs, (bool, np.bool_)) or not isinstance(n_inputs, (int, np.integer)):
+            raise TypeError(f"n_inputs {n_inputs!r} is not an integer")
+        if not 2 <= n_inputs <= cls.MAX_INPUTS or n_inputs % 2:
+            raise ValueError(f"n_inputs must be even and 2..{cls.MAX_INPUTS}")
+        return int(n_inputs)
+
+    @classmethod
+    def quad_table(cls, inputs, n_inputs: int) -> Tuple[np.ndarray, np.ndarray]:
+        """``(quad_antennas, quads)``, int32 (n_quads, 2) and (n_quads, 4), of `inputs`
+        (baselines x 2, as :meth:`SolveGainsHost.pair_table` takes them). A baseline ``(p, q)``
+        with ``p // 2 <= q // 2`` is entry ``(p % 2, q % 2)`` of quad ``(p // 2, q // 2)``,
+        positive; any other is entry ``(q % 2, p % 2)`` of quad ``(q // 2, p // 2)``, negative.
+        A baseline with an index outside ``0..n_inputs-1`` belongs to no quad. The quads are
+        ordered by the smallest baseline index they name. ``ValueError`` for an entry that is
+        filled twice and when no baseline was placed."""
+        n_inputs = cls.check_n_inputs(n_inputs)
+        inputs = np.asarray(inputs)
+        if inputs.ndim != 2 or inputs.shape[1] != 2 or inputs.dtype.kind not in "iu":
+            raise ValueError(f"inputs must be integers of shape (baselines, 2), not "
+                             f"{inputs.dtype.name} {inputs.shape}")  # fmt: skip
+        if len(inputs) >= 2**31:
+            raise ValueError("inputs lists more than 2^31 - 1 baselines")
+        table = {}  # (a, b) -> its four entries; insertion order is the order of the quads
+        for j, (p, q) in enumerate(inputs.tolist()):
+            if not (0 <= p < n_inputs and 0 <= q < n_inputs):
+                continue
+            if p // 2 <= q // 2:
+                key, entry, value = (p // 2, q // 2), 2 * (p % 2) + q % 2, j + 1
+            else:
+                key, entry, value = (q // 2, p // 2), 2 * (q % 2) + p % 2, -(j + 1)
+            row = table.setdefault(key, [0, 0, 0, 0])
+            if row[entry] != 0:
+                raise ValueError(f"inputs lists the pair ({2 * key[0] + entry // 2}, "
+                                 f"{2 * key[1] + entry % 2}) twice: baselines "
+                                 f"{abs(row[entry]) - 1} and {j}")  # fmt: skip
+            row[entry] = value
+        if not table:
+            raise ValueError("inputs lists no baseline between inputs 0..n_inputs-1")
+        quad_antennas = np.array(list(table.keys()), np.int32).reshape(-1, 2)
+        quads = np.array(list(table.values()), np.int32).reshape(-1, 4)
+        return quad_antennas, quads
+
+    @staticmethod
+    def _add(a, b):
+        """``a + b`` on (re, im) pairs."""
+        return a[0] + b[0], a[1] + b[1]
+
+    def __call__(self, vis: np.ndarray, jones: np.ndarray, quad_antennas: np.ndarray,
+                 quads: np.ndarray, weights: Optional[np.ndarray] = None,
+                 flags: Optional[np.ndarray] = None):  # fmt: skip
+        """``(out_vis, out_weights or None, out_flags or None)`` for complex64 `vis` (channels,
+        baselines), complex64 `jones` (channels, n_inputs, 2), int32 `quad_antennas`
+        (n_quads, 2), int32 `quads` (n_quads, 4), optional float32 `weights` and optional uint8
+        `flags` (both channels, baselines). ``ValueError``, naming the argument, for a wrong
+        dtype, rank or shape (channels, baselines and n_quads at least 1, n_inputs even and
+        2..2048), and if `quads` names one baseline in two present entries. No argument is
+        modified."""
+        vis = _check_array("vis", vis, np.complex64, "(channels, baselines)",
+                           lambda s: len(s) == 2 and s[0] >= 1 and s[1] >= 1)  # fmt: skip
+        channels, baselines = vis.shape
+        jones = _check_array("jones", jones, np.complex64,
+                             "(channels, n_inputs, 2), n_inputs even and 2..2048",
+                             lambda s: len(s) == 3 and s[0] == channels and s[2] == 2
+                             and s[1] % 2 == 0 and 2 <= s[1] <= self.MAX_INPUTS)  # fmt: skip
+        quad_antennas = _check_array("quad_antennas", quad_antennas, np.int32, "(n_quads, 2)",
+                                     lambda s: len(s) == 2 and s[0] >= 1 and s[1] == 2)  # fmt: skip
+        n_quads = quad_antennas.shape[0]
+        quads = _check_array("quads", quads, np.int32, "(n_quads, 4)",
+                             lambda s: s == (n_quads, 4))  # fmt: skip
+        if weights is not None:
+            weights = _check_array("weights", weights, np.float32, "(channels, baselines)",
+                                   lambda s: s == vis.shape)  # fmt: skip
+        if flags is not None:
+            flags = _check_array("flags", flags, np.uint8, "(channels, baselines)",
+                                 lambda s: s == vis.shape)  # fmt: skip
+        n_ant = jones.shape[1] // 2
+        f32 = np.float32
+        t = quads.astype(np.int64)
+        present = (t != 0) & (np.abs(t) <= baselines)
+        named = np.abs(t[present]) - 1
+        counts = np.bincount(named, minlength=1)
+        if (counts > 1).any():
+            raise ValueError(f"quads names baseline {int(np.argmax(counts > 1))} in more than "
+                             f"one entry")  # fmt: skip
+        a, b = quad_antennas[:, 0].astype(np.int64), quad_antennas[:, 1].astype(np.int64)
+        inr = (a >= 0) & (a < n_ant) & (b >= 0) & (b < n_ant)
+        # where each of the four sources comes from: its own entry, or (one dish) its mirror
+        source = np.tile(np.arange(4), (n_quads, 1))
+        stand = np.zeros((n_quads, 4), bool)
+        for entry, other in ((1, 2), (2, 1)):
+            stand[:, entry] = (a == b) & ~present[:, entry] & present[:, other]
+            source[stand[:, entry], entry] = other
+        t_src = np.take_along_axis(t, source, axis=1)
+        have = present | stand
+        j_src = np.where(have, np.abs(t_src) - 1, 0)
+        complete = inr & have.all(axis=1)
+        rows_a = 2 * np.where(inr, a, 0)
+        rows_b = 2 * np.where(inr, b, 0)
+        mul, mul_conj, add = SolveJonesHost._mul, SolveJonesHost._mul_conj, self._add
+        with np.errstate(all="ignore"):
+            # C_a[i][m], C_b[k][n] as (re, im) pairs of (channels, n_quads)
+            ca = [[(jones.real[:, rows_a + i, m], jones.imag[:, rows_a + i, m])
+                   for m in range(2)] for i in range(2)]  # fmt: skip
+            cb = [[(jones.real[:, rows_b + k, n], jones.imag[:, rows_b + k, n])
+                   for n in range(2)] for k in range(2)]  # fmt: skip
+            nan = np.zeros((channels, n_quads), bool)
+            for matrix in (ca, cb):
+                for row in matrix:
+                    for re, im in row:
+                        nan |= np.isnan(re) | np.isnan(im)
+            ok = complete[np.newaxis, :] & ~nan
+            s, w = [], []
+            for entry in range(4):
+                re, im = vis.real[:, j_src[:, entry]], vis.imag[:, j_src[:, entry]]
+                im = np.where(t_src[:, entry] < 0, -im, im)
+                im = np.where(stand[:, entry], -im, im)
+                s.append((re, im))
+                if weights is not None:
+                    w.append(np.where(have[:, entry], weights[:, j_src[:, entry]], f32(1)))
+            # T[i][n], then O[i][k]
+            tt = [[add(mul(ca[i][0], s[n]), mul(ca[i][1], s[2 + n])) for n in range(2)]
+                  for i in range(2)]  # fmt: skip
+            out = [[add(mul_conj(tt[i][0], cb[k][0]), mul_conj(tt[i][1], cb[k][1]))
+                    for k in range(2)] for i in range(2)]  # fmt: skip
+            assert out[0][0][0].dtype == f32
+            out_vis = vis.copy()
+            out_weights = None
+            if weights is not None:
+                out_weights = weights.copy()
+                all_w = (w[0] > 0) & (w[1] > 0) & (w[2] > 0) & (w[3] > 0)
+                r = [f32(1) / x for x in w]
+                norm2 = SolveJonesHost._norm2
+                al = [[norm2(ca[i][m]) for m in range(2)] for i in range(2)]
+                be = [[norm2(cb[k][n]) for n in range(2)] for k in range(2)]
+                u = [[al[i][0] * r[n] + al[i][1] * r[2 + n] for n in range(2)] for i in range(2)]
+                var = [[u[i][0] * be[k][0] + u[i][1] * be[k][1] for k in range(2)]
+                       for i in range(2)]  # fmt: skip
+                assert var[0][0].dtype == f32
+            out_flags = None
+            if flags is not None:
+                out_flags = flags.copy()
+                any_f = np.zeros((channels, n_quads), np.uint8)
+                for entry in range(4):
+                    any_f |= np.where(present[:, entry], flags[:, j_src[:, entry]], np.uint8(0))
+                any_f |= np.where(ok, np.uint8(0), np.uint8(self.flag_value))
+            for entry in range(4):
+                i, k = divmod(entry, 2)
+                sel = present[:, entry]
+                j = j_src[sel, entry]
+                good = ok[:, sel]
+                o_re, o_im = out[i][k][0][:, sel], out[i][k][1][:, sel]
+                o_im = np.where(t[sel, entry] < 0, -o_im, o_im)
+                out_vis.real[:, j] = np.where(good, o_re, vis.real[:, j])
+                out_vis.imag[:, j] = np.where(good, o_im, vis.imag[:, j])
+                if weights is not None:
+                    v = var[i][k][:, sel]
+                    scaled = good & all_w[:, sel] & (v > 0)
+                    out_weights[:, j] = np.where(scaled, f32(1) / np.where(scaled, v, f32(1)),
+                                                 f32(0))  # fmt: skip
+                if flags is not None:
+                    out_flags[:, j] = any_f[:, sel]
+        return out_vis, out_weights, out_flags
+
+
 class PredictHost:
     """Model visibilities of point sources and, optionally, the data divided by them: the step
     in front of :class:`SolveGainsHost` for a calibrator that is not a unit source at the phase

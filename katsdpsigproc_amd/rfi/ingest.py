@@ -28,7 +28,10 @@ place, in one launch with one workgroup per input, bit for bit what
 both: per input, the solved gains with the delay divided out, smoothed, normalised, filled
 across the channels the solver lost, and recombined with the delay and a band-wide gain, in one
 launch with one workgroup per input, bit for bit what :class:`.host.InterpolateGainsHost`
-defines. The classes follow DESIGN.md, "Adding an operation".
+defines. And the step that closes the dual-polarisation chain: the per-antenna 2x2 Jones
+matrices of the leakage solve applied to the four products of every antenna pair, with the
+weights propagated and the flags ORed over the pair, in one launch, in place or not, bit for bit
+what :class:`.host.ApplyJonesHost` defines. The classes follow DESIGN.md, "Adding an operation".
 """
 
 import ctypes
@@ -851,6 +854,173 @@ class SolveJonesHostFromDevice:
         out = _native_op.run_once(fn, self.command_queue, given,
                                   ["jones", "iterations", "status"])  # fmt: skip
         return out[0], out[1], out[2]
+
+
+class ApplyJonesTemplate(_native_op.NativeTemplate):
+    """The step that closes the dual-polarisation chain: the per-antenna 2x2 matrices that
+    :class:`SolveJonesTemplate` leaves with ``corrections=True`` applied to the ``vis`` that
+    :class:`.device.Finalise` leaves, ``C_a V_ab C_b^H`` on the four products of every antenna
+    pair, the ``weights`` propagated and the samples without a correction flagged, in one
+    kernel launch; see :class:`host.ApplyJonesHost` for every step. The matrices are small
+    (channels x inputs x 2) and stay on the device; only their application is per sample.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    weights
+        ``True``: there are a `weights` and an `out_weights` slot
+    flags
+        ``True``: there are a `flags` and an `out_flags` slot
+    flag_value
+        As for :class:`host.ApplyJonesHost` (same errors)
+    tuning
+        The kernel picks its launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.ApplyJonesHost
+    KERNEL = "ksp_apply_jones"
+
+    def __init__(self, context: AbstractContext, weights: bool = True, flags: bool = True,
+                 flag_value: int = 128, tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        self.weights = bool(weights)
+        self.flags = bool(flags)
+        self.flag_value = host.ApplyJonesHost(flag_value).flag_value
+        self._setup(context, tuning)
+
+
+class ApplyJones(_native_op.NativeOperation):
+    """Concrete :class:`ApplyJonesTemplate` (``ValueError`` if `channels`, `baselines` or
+    `n_quads` is below 1 or `n_inputs` odd or outside 2..2048; ``TypeError`` if `n_inputs` or
+    `n_quads` is not an integer).
+
+    .. rubric:: Slots
+
+    **vis**, **out_vis** : channels x baselines, complex64
+    **weights**, **out_weights** : channels x baselines, float32 (only with ``weights``)
+    **flags**, **out_flags** : channels x baselines, uint8 (only with ``flags``)
+    **jones** : channels x n_inputs x 2, complex64: the matrices that multiply
+    **quad_antennas** : n_quads x 2, int32, contiguous
+    **quads** : n_quads x 4, int32, contiguous (:meth:`host.ApplyJonesHost.quad_table`)
+
+    Every padded dimension is an object of its own, so ``jones`` can be compounded with
+    :class:`SolveJones`' output, ``vis``, ``weights`` and ``flags`` with
+    :class:`.device.Finalise`'s outputs and the ``out_*`` slots with the inputs of
+    :class:`CompressWeights`, :class:`RangePercentiles` or the 2-D flagger, each taking the
+    other's padding; the last axis of ``jones`` and of the two tables is never padded. Binding
+    one buffer to ``vis`` and ``out_vis`` (and likewise to the other two pairs) applies the
+    matrices in place; with buffers of their own the inputs are left untouched, and so are the
+    output elements of a baseline that no quad names.
+    """
+
+    def __init__(self, template: ApplyJonesTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int, n_inputs: int, n_quads: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, baselines, allocator)
+        if channels < 1 or baselines < 1:
+            raise ValueError("channels and baselines must be at least 1")
+        self.n_inputs = host.ApplyJonesHost.check_n_inputs(n_inputs)
+        if isinstance(n_quads, (bool, np.bool_)) or not isinstance(n_quads, (int, np.integer)):
+            raise TypeError(f"n_quads {n_quads!r} is not an integer")
+        if n_quads < 1:
+            raise ValueError("n_quads must be at least 1")
+        self.n_quads = int(n_quads)
+
+        def pair(name: str, dtype) -> None:
+            for slot in (name, "out_" + name):
+                self.slots[slot] = accel.IOSlot((channels, accel.Dimension(baselines)), dtype)
+
+        pair("vis", np.complex64)
+        if template.weights:
+            pair("weights", np.float32)
+        if template.flags:
+            pair("flags", np.uint8)
+        self.slots["jones"] = accel.IOSlot(
+            (channels, accel.Dimension(n_inputs), accel.Dimension(2, exact=True)), np.complex64)  # fmt: skip
+        self.slots["quad_antennas"] = accel.IOSlot(
+            (accel.Dimension(n_quads), accel.Dimension(2, exact=True)), np.int32)  # fmt: skip
+        self.slots["quads"] = accel.IOSlot(
+            (accel.Dimension(n_quads), accel.Dimension(4, exact=True)), np.int32)  # fmt: skip
+
+    def _run(self) -> None:
+        template = self.template
+        vis, out_vis = self.buffer("vis"), self.buffer("out_vis")
+        weights = self.buffer("weights") if template.weights else None
+        out_weights = self.buffer("out_weights") if template.weights else None
+        flags = self.buffer("flags") if template.flags else None
+        out_flags = self.buffer("out_flags") if template.flags else None
+        jones = self.buffer("jones")
+        self._launch(
+            vis.buffer,
+            _native_op.pointer(weights),
+            _native_op.pointer(flags),
+            jones.buffer,
+            self.buffer("quad_antennas").buffer,
+            self.buffer("quads").buffer,
+            out_vis.buffer,
+            _native_op.pointer(out_weights),
+            _native_op.pointer(out_flags),
+            np.int32(self.channels),
+            np.int32(self.baselines),
+            np.int32(self.n_inputs),
+            np.int32(self.n_quads),
+            np.int32(vis.padded_shape[1]),
+            _native_op.stride(weights),
+            _native_op.stride(flags),
+            np.int32(jones.padded_shape[1]),
+            np.int32(out_vis.padded_shape[1]),
+            _native_op.stride(out_weights),
+            _native_op.stride(out_flags),
+            np.int32(template.flag_value),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        template = self.template
+        return self._parameters(weights=template.weights, flags=template.flags,
+                                flag_value=template.flag_value, n_inputs=self.n_inputs,
+                                n_quads=self.n_quads)  # fmt: skip
+
+
+ApplyJonesTemplate.operation_class = ApplyJones
+
+
+class ApplyJonesHostFromDevice:
+    """Make an :class:`ApplyJonesTemplate` callable like :class:`host.ApplyJonesHost`, but with
+    the ``inputs`` (baselines x 2) that :class:`SolveJonesHostFromDevice` takes instead of the
+    table, which it builds (:meth:`host.ApplyJonesHost.quad_table`): ``(vis, jones, inputs,
+    weights=None, flags=None)`` in, ``(out_vis, out_weights or None, out_flags or None)`` out;
+    allocates on every call. The device outputs start as copies of the inputs, so a baseline
+    that no quad names passes through, as with the host class. ``TypeError`` unless `weights`
+    and `flags` are each given exactly when the template has them."""
+
+    def __init__(self, template: ApplyJonesTemplate, command_queue: AbstractCommandQueue) -> None:
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, vis: np.ndarray, jones: np.ndarray, inputs: np.ndarray,
+                 weights: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None
+                 ) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:  # fmt: skip
+        template = self.template
+        _native_op.check_optional(weights, template.weights, "weights")
+        _native_op.check_optional(flags, template.flags, "flags")
+        channels, baselines = vis.shape
+        if np.shape(inputs) != (baselines, 2):
+            raise ValueError(f"inputs must have shape (baselines, 2) = ({baselines}, 2), "
+                             f"not {np.shape(inputs)}")  # fmt: skip
+        if np.ndim(jones) != 3:
+            raise ValueError(f"jones must have shape (channels, n_inputs, 2), not {np.shape(jones)}")
+        n_inputs = int(np.shape(jones)[1])
+        quad_antennas, quads = host.ApplyJonesHost.quad_table(inputs, n_inputs)
+        fn = template.instantiate(self.command_queue, channels, baselines, n_inputs, len(quads))
+        given = {"vis": vis, "jones": jones, "quad_antennas": quad_antennas, "quads": quads,
+                 "weights": weights, "flags": flags, "out_vis": vis, "out_weights": weights,
+                 "out_flags": flags}  # fmt: skip
+        outputs = ["out_vis"] + (["out_weights"] if template.weights else []) + (
+            ["out_flags"] if template.flags else [])  # fmt: skip
+        out = _native_op.run_once(fn, self.command_queue, given, outputs)
+        return (out[0], out[1] if template.weights else None,
+                out[-1] if template.flags else None)  # fmt: skip
 
 
 class PredictTemplate(_native_op.NativeTemplate):
