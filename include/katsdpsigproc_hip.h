@@ -832,6 +832,58 @@ int ksp_interpolate_gains(int device, void *stream, const void *gains, const uin
                           int out_stride, int max_gap, int smooth, int status_mask,
                           int corrections);
 
+/* interpolate_jones: per antenna, the 2x2 matrices that ksp_solve_jones leaves (corrections 0),
+ * filled across the channels it left without a matrix, as a table that ksp_apply_jones can
+ * apply to another scan, in one launch: the 2x2 counterpart of ksp_interpolate_gains, with its
+ * arithmetic (no reference counterpart; bit for bit what rfi/host.py InterpolateJonesHost
+ * computes; every step one float32 operation, rounded once, never an fma).
+ * jones, out: complex64 [channels][stride][2], of which n_inputs rows of two per channel are
+ * data: row 2a + i is row i of antenna a's matrix, and the strides count such rows, as in
+ * ksp_solve_jones; model: complex64 [channels][model_stride], what ksp_fit_delays writes with
+ * corrections 0, or NULL; status: uint8 [channels] or NULL; scale: complex64 [n_inputs] or
+ * NULL; kept, filled: int32 [n_inputs / 2]; fill_status: uint8 [n_inputs / 2]; mean_amplitude:
+ * float32 [n_inputs / 2], or NULL for no normalisation. Per antenna a, with
+ * z[i][k] = jones[c][2a + i][k] and m_i = model[c][2a + i]:
+ *   1. c is kept if all eight floats of z are finite, (status is NULL or
+ *      status[c] & status_mask == 0) and (model is NULL or all four floats of m_0 and m_1 are
+ *      finite), else missing: one mask per antenna; kept[a] counts the kept ones; none: bit 0
+ *      of fill_status[a].
+ *   2. d[i][k] = z[i][k] conj(m_i) as step 2 of ksp_interpolate_gains, or z without model.
+ *   3. per element, step 3 of ksp_interpolate_gains (the four elements share the count).
+ *   4. with mean_amplitude: nik = s[i][k].re s[i][k].re + s[i][k].im s[i][k].im;
+ *      term = sqrt(((n00 + n01) + (n10 + n11)) 0.5) per kept channel; a = (the halving tree of
+ *      ksp_interpolate_gains over Cpad terms) / float(kept[a]); mean_amplitude[a] = a, NaN if
+ *      no channel is kept; a in (0, inf): all eight floats of s are divided by a, else bit 0.
+ *   5. per element, step 5 of ksp_interpolate_gains with one l, r and t for the four elements;
+ *      filled[a] counts the missing channels that got a matrix; a gap left is bit 1.
+ *   6. with model, y[i][k] = y[i][k] m_i at every channel;
+ *   7. with scale, y[i][k] = y[i][k] scale[2a + i];
+ *   8. corrections 1: D = y00 y11 - y01 y10; q = D.re D.re + D.im D.im;
+ *      inv = (D.re / q, -D.im / q); out = [[y11 inv, -(y01 inv)], [-(y10 inv), y00 inv]] (the
+ *      products are negated), NaN in all four elements unless q > 0.
+ *   An antenna with bit 0 has NaN in all its elements of out, filled[a] = 0 and no other bit.
+ * channels is 1..16384, n_inputs even and 2..2048, max_gap 0..16384, smooth odd and 1..31,
+ * status_mask 0..255, corrections 0 or 1. out may be jones itself (same pointer and stride) but
+ * must not overlap it otherwise, and shares no byte with model. jones and out need the
+ * alignment of a complex64 only. Rows between n_inputs and a stride are neither read nor
+ * written. One kernel launch, one workgroup per antenna with 8 channels bytes of LDS, no
+ * workspace, no atomics. Every argument is checked before any device call. */
+int ksp_interpolate_jones(int device, void *stream, const void *jones, const uint8_t *status,
+                          const void *model, const void *scale, void *out, int *kept,
+                          int *filled, uint8_t *fill_status, float *mean_amplitude,
+                          int channels, int n_inputs, int jones_stride, int model_stride,
+                          int out_stride, int max_gap, int smooth, int status_mask,
+                          int corrections);
+
+/* jones_diagonal: gains[c][p] = jones[c][p][p % 2], a copy of bits: the diagonal of every
+ * antenna's matrix as the per-input gains that ksp_fit_delays reads. jones: complex64
+ * [channels][jones_stride][2] (strides in rows of two, as above); gains: complex64
+ * [channels][gains_stride]. channels and n_inputs are at least 1; gains shares no byte with
+ * jones. Elements between n_inputs and a stride are neither read nor written. One kernel
+ * launch. Every argument is checked before any device call. */
+int ksp_jones_diagonal(int device, void *stream, const void *jones, void *gains, int channels,
+                       int n_inputs, int jones_stride, int gains_stride);
+
 /* range_percentiles: per channel and per range of baselines, the [0, 100, 25, 75, 50] %
  * amplitudes ("lower" element) of the samples that are neither NaN nor flagged under a mask,
  * how many those are, and the OR of the range's flags, all ranges in one launch (no reference

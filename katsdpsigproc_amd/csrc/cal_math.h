@@ -1,8 +1,8 @@
 // Device arithmetic the calibration kernels share (apply_gains, solve_gains, solve_jones, predict,
-// fit_delays, interpolate_gains). Each kernel reproduces a host class of rfi/host.py bit for bit, so every
-// helper is one float operation per written step, in the order written, with intrinsics that
-// are never contracted; a helper stands only where a kernel's expression is operation for
-// operation this one. Device code only.
+// fit_delays, interpolate_gains, interpolate_jones). Each kernel reproduces a host class of
+// rfi/host.py bit for bit, so every helper is one float operation per written step, in the order
+// written, with intrinsics that are never contracted; a helper stands only where a kernel's
+// expression is operation for operation this one. Device code only.
 #pragma once
 #include "ksp_common.h"
 

@@ -2120,6 +2120,216 @@ class InterpolateGainsHost:
         return out, n_kept, filled, fill_status, mean_amplitude
 
 
+class InterpolateJonesHost(InterpolateGainsHost):
+    """The 2x2 counterpart of :class:`InterpolateGainsHost`: the matrices that
+    :class:`SolveJonesHost` solves on a calibrator (``corrections=False``), made into a table
+    that :class:`ApplyJonesHost` can apply to a target. Per antenna, the channels the solver
+    left without a matrix are filled from their neighbours across gaps of at most `max_gap`
+    channels; a matrix is interpolated whole or not at all. No reference counterpart; this
+    class is the definition that the device operation
+    (:class:`.ingest.InterpolateJonesTemplate`) matches bit for bit.
+
+    The parameters, their checks, :attr:`NO_DATA` and :attr:`GAP_LEFT` are those of
+    :class:`InterpolateGainsHost`, and so is the arithmetic: one float32 operation per step,
+    rounded once, real and imaginary parts apart, the complex products as written there and in
+    :class:`SolveJonesHost`. ``jones[c, 2a + i, k]`` is element ``(i, k)`` of antenna ``a``'s
+    matrix. Per antenna ``a``, with ``z[i][k] = jones[c, 2a + i, k]`` and ``m_i = model[c, 2a +
+    i]`` (one unit phasor per feed, what :class:`FitDelaysHost` fits to the diagonal that
+    :class:`JonesDiagonalHost` extracts):
+
+    1. *Kept channels.* ``c`` is kept if all eight floats of the matrix are finite, `status` is
+       absent or ``status[c] & status_mask == 0``, and `model` is absent or all four floats of
+       ``m_0``, ``m_1`` are finite. One mask per antenna. ``kept[a]`` counts the kept channels;
+       none sets bit 0.
+    2. *De-rotate.* ``d[i][k] = z[i][k]*conj(m_i)`` (step 2 there), ``d = z`` without `model`.
+       After the solver's referencing, element ``(i, k)`` winds with the delay of feed ``i`` of
+       ``a`` minus that of feed ``k`` of the reference antenna; the per-row model removes all
+       of it from the diagonal and leaves the reference antenna's own cross-feed delay on the
+       leakage terms.
+    3. *Smooth.* Per element, step 3 there; the four elements share the count.
+    4. *Normalise* (with `normalise`). Per kept channel ``term = sqrt(((n00 + n01) + (n10 +
+       n11))*0.5)`` with ``nik = s.re*s.re + s.im*s.im`` of element ``(i, k)``; ``a`` is the
+       halving tree of the terms over ``Cpad`` divided by float32 of ``kept[a]``, as there;
+       ``mean_amplitude[a] = a``, NaN with nothing kept. If ``a`` is in ``(0, inf)`` all eight
+       floats are divided by it, otherwise bit 0 is set. An identity matrix has amplitude 1.
+    5. *Fill.* Per element, step 5 there, with the same ``l``, ``r`` and ``t`` for the four
+       elements. ``filled[a]`` counts the missing channels that got a matrix.
+    6. *Re-rotate.* ``y[i][k] = y[i][k]*m_i`` at every channel.
+    7. *Scale.* ``y[i][k] = y[i][k]*scale[2a + i]``.
+    8. *Corrections.* As in :class:`SolveJonesHost`: with ``[[a, b], [c, d]] = y``, ``D = a*d -
+       b*c``, ``s = D.re*D.re + D.im*D.im``, ``inv = (D.re/s, -D.im/s)`` and the matrix becomes
+       ``[[d*inv, -(b*inv)], [-(c*inv), a*inv]]`` (the products are negated, not the factor);
+       all four elements are NaN unless ``s > 0``.
+
+    An antenna with bit 0 has NaN in all its elements of ``out``, ``filled[a] = 0`` and no
+    other bit. With ``smooth=1`` and without `model`, `scale`, `normalise` and `corrections`,
+    ``out`` equals ``jones`` bit for bit on every kept channel. On exactly diagonal matrices
+    whose two feeds have the same kept channels, and without `corrections` and `normalise` (the
+    amplitude of a matrix is not that of one of its elements), the diagonal of ``out`` is
+    :class:`InterpolateGainsHost`'s ``out`` for those inputs bit for bit and the off-diagonals
+    stay zero.
+    """
+
+    MAX_INPUTS = ApplyJonesHost.MAX_INPUTS
+
+    @classmethod
+    def check_shape(cls, channels: int, n_inputs: int) -> None:
+        """``ValueError`` if `channels` is outside 1..16384 or `n_inputs` is odd or outside
+        2..2048."""
+        if not 1 <= channels <= cls.MAX_CHANNELS:
+            raise ValueError(f"channels must be 1..{cls.MAX_CHANNELS}")
+        ApplyJonesHost.check_n_inputs(n_inputs)
+
+    def __call__(self, jones: np.ndarray, status: Optional[np.ndarray] = None,
+                 model: Optional[np.ndarray] = None, scale: Optional[np.ndarray] = None):  # fmt: skip
+        """``(out, kept, filled, fill_status, mean_amplitude)``: complex64 (channels, n_inputs,
+        2), int32, int32 and uint8 (n_inputs // 2,), and float32 (n_inputs // 2,) with
+        `normalise`, else ``None``; for complex64 `jones` (channels, n_inputs, 2), optional
+        uint8 `status` (channels,), optional complex64 `model` (channels, n_inputs) and
+        optional complex64 `scale` (n_inputs,). ``ValueError``, naming the argument, for a
+        wrong dtype, rank or shape (channels 1..16384, n_inputs even and 2..2048). No argument
+        is modified."""
+        jones = _check_array("jones", jones, np.complex64, "(channels, n_inputs, 2)",
+                             lambda s: len(s) == 3 and 1 <= s[0] <= self.MAX_CHANNELS
+                             and s[1] % 2 == 0 and 2 <= s[1] <= self.MAX_INPUTS
+                             and s[2] == 2)  # fmt: skip
+        channels, n_inputs = jones.shape[:2]
+        n_ant = n_inputs // 2
+        if status is not None:
+            status = _check_array("status", status, np.uint8, "(channels,)",
+                                  lambda s: s == (channels,))  # fmt: skip
+        if model is not None:
+            model = _check_array("model", model, np.complex64, "(channels, n_inputs)",
+                                 lambda s: s == (channels, n_inputs))  # fmt: skip
+        if scale is not None:
+            scale = _check_array("scale", scale, np.complex64, "(n_inputs,)",
+                                 lambda s: s == (n_inputs,))  # fmt: skip
+        f32 = np.float32
+        nan, one = f32(np.nan), f32(1)
+        # element e = 2 i + k of every antenna, (channels, n_ant) per part; row i has model i
+        z = [(jones.real[:, i::2, k], jones.imag[:, i::2, k]) for i in (0, 1) for k in (0, 1)]
+        kept = np.ones((channels, n_ant), bool)
+        for re, im in z:
+            kept &= np.isfinite(re) & np.isfinite(im)
+        if status is not None:
+            kept &= ((status & np.uint8(self.status_mask)) == 0)[:, np.newaxis]
+        m = None
+        if model is not None:
+            m = [(model.real[:, i::2], model.imag[:, i::2]) for i in (0, 1)]
+            for re, im in m:
+                kept &= np.isfinite(re) & np.isfinite(im)
+        n_kept = kept.sum(axis=0).astype(np.int32)
+        failed = n_kept == 0
+        mean_amplitude = None
+        with np.errstate(all="ignore"):
+            s = z
+            if m is not None:
+                s = [(re * m[e // 2][0] + im * m[e // 2][1], im * m[e // 2][0] - re * m[e // 2][1])
+                     for e, (re, im) in enumerate(s)]  # fmt: skip
+            if self.smooth > 1:
+                reach = self.smooth // 2
+                sums = [[np.zeros(kept.shape, f32), np.zeros(kept.shape, f32)] for _ in s]
+                count = np.zeros(kept.shape, np.int32)
+                for offset in range(-reach, reach + 1):  # channel c + offset, ascending
+                    lo, hi = max(0, -offset), min(channels, channels - offset)
+                    if lo >= hi:
+                        continue
+                    to, of = slice(lo, hi), slice(lo + offset, hi + offset)
+                    for total, parts in zip(sums, s):
+                        for i in range(2):
+                            total[i][to] = np.where(kept[of], total[i][to] + parts[i][of],
+                                                    total[i][to])  # fmt: skip
+                    count[to] += kept[of]
+                number = np.maximum(count, 1).astype(f32)  # (only kept channels are used)
+                s = [(total[0] / number, total[1] / number) for total in sums]
+            if self.normalise:
+                c_pad = 1
+                while c_pad < channels:
+                    c_pad *= 2
+                n2 = [re * re + im * im for re, im in s]
+                terms = np.zeros((c_pad, n_ant), f32)
+                terms[:channels] = np.where(
+                    kept, np.sqrt(((n2[0] + n2[1]) + (n2[2] + n2[3])) * f32(0.5)), f32(0))
+                total = FitDelaysHost._tree_sum(terms)
+                mean_amplitude = np.where(failed, nan, total / np.maximum(n_kept, 1).astype(f32))
+                usable = (mean_amplitude > 0) & (mean_amplitude < np.inf)
+                safe = np.where(usable, mean_amplitude, one)
+                s = [(re / safe, im / safe) for re, im in s]
+                failed = failed | ~usable
+                assert mean_amplitude.dtype == f32
+            # the nearest kept channel at or below and at or above every channel
+            index = np.arange(channels, dtype=np.int64)[:, np.newaxis]
+            none_above = np.int64(channels)
+            below = np.maximum.accumulate(np.where(kept, index, -1), axis=0)
+            above = np.minimum.accumulate(np.where(kept, index, none_above)[::-1], axis=0)[::-1]
+            has_l, has_r = below >= 0, above < none_above
+            l, r = np.maximum(below, 0), np.minimum(above, channels - 1)
+            span = np.where(has_l & has_r & ~kept, r - l, 1)
+            t = (index - l).astype(f32) / span.astype(f32)
+            between = has_l & has_r & (above - below - 1 <= self.max_gap)
+            held_l = has_l & ~has_r & (index - below <= self.max_gap)
+            held_r = has_r & ~has_l & (above - index <= self.max_gap)
+            got = ~kept & (between | held_l | held_r)
+            y = []
+            for e, parts in enumerate(s):
+                filled_parts = []
+                for part in parts:
+                    sl, sr = np.take_along_axis(part, l, 0), np.take_along_axis(part, r, 0)
+                    value = np.where(between, sl + (sr - sl) * t,
+                                     np.where(held_l, sl, np.where(held_r, sr, nan)))  # fmt: skip
+                    filled_parts.append(np.where(kept, part, value))
+                y_re, y_im = filled_parts
+                if m is not None:
+                    y_re, y_im = self._product(y_re, y_im, m[e // 2][0], m[e // 2][1])
+                if scale is not None:
+                    y_re, y_im = self._product(y_re, y_im, scale.real[np.newaxis, e // 2 :: 2],
+                                               scale.imag[np.newaxis, e // 2 :: 2])  # fmt: skip
+                y.append((y_re, y_im))
+            if self.corrections:
+                ja, jb, jc, jd = y
+                ad, bc = self._product(*ja, *jd), self._product(*jb, *jc)
+                big_d = (ad[0] - bc[0], ad[1] - bc[1])
+                q = big_d[0] * big_d[0] + big_d[1] * big_d[1]
+                pos = q > 0
+                safe = np.where(pos, q, one)  # (no 0 / 0 where the quotient is not used)
+                inv = (big_d[0] / safe, -big_d[1] / safe)
+                di, bi = self._product(*jd, *inv), self._product(*jb, *inv)
+                ci, ai = self._product(*jc, *inv), self._product(*ja, *inv)
+                y = [tuple(np.where(pos, part, nan) for part in parts)
+                     for parts in (di, (-bi[0], -bi[1]), (-ci[0], -ci[1]), ai)]  # fmt: skip
+            assert all(part.dtype == f32 for parts in y for part in parts)
+        out = np.empty(jones.shape, np.complex64)
+        for e, (y_re, y_im) in enumerate(y):
+            out.real[:, e // 2 :: 2, e % 2] = np.where(failed, nan, y_re)
+            out.imag[:, e // 2 :: 2, e % 2] = np.where(failed, nan, y_im)
+        filled = np.where(failed, 0, got.sum(axis=0)).astype(np.int32)
+        fill_status = np.where(failed, self.NO_DATA,
+                               np.where((~kept & ~got).any(axis=0), self.GAP_LEFT, 0)
+                               ).astype(np.uint8)  # fmt: skip
+        return out, n_kept, filled, fill_status, mean_amplitude
+
+
+class JonesDiagonalHost:
+    """The diagonal of every antenna's matrix as per-input gains: ``gains[c, p] = jones[c, p,
+    p % 2]``, a copy of bits. It is what :class:`FitDelaysHost` reads to fit one delay per feed
+    to the table of :class:`SolveJonesHost` (after whose referencing the reference antenna's
+    diagonal is real and positive, so that its fitted phasor is 1 and the delays of all feeds
+    are defined against it); the `model` it writes is the one :class:`InterpolateJonesHost`
+    takes. The device operation is :class:`.ingest.JonesDiagonalTemplate`."""
+
+    def __call__(self, jones: np.ndarray) -> np.ndarray:
+        """complex64 (channels, n_inputs) for complex64 `jones` (channels, n_inputs, 2) with
+        at least one channel and one input; ``ValueError`` otherwise."""
+        jones = _check_array("jones", jones, np.complex64, "(channels, n_inputs, 2)",
+                             lambda s: len(s) == 3 and s[0] >= 1 and s[1] >= 1
+                             and s[2] == 2)  # fmt: skip
+        n_inputs = jones.shape[1]
+        gains = np.empty(jones.shape[:2], np.complex64)
+        gains.view(np.uint64)[...] = np.ascontiguousarray(jones).view(np.uint64)[
+            :, np.arange(n_inputs), np.arange(n_inputs) % 2]  # fmt: skip
+        return gains
+
+
 def check_ranges(ranges, baselines: Optional[int] = None) -> Tuple[Tuple[int, int], ...]:
     """`ranges` as a tuple of 1 to :attr:`RangePercentilesHost.MAX_RANGES` pairs of ints
     ``(start, stop)`` with ``0 <= start <= stop``, ``stop - start`` at most

@@ -31,7 +31,11 @@ launch with one workgroup per input, bit for bit what :class:`.host.InterpolateG
 defines. And the step that closes the dual-polarisation chain: the per-antenna 2x2 Jones
 matrices of the leakage solve applied to the four products of every antenna pair, with the
 weights propagated and the flags ORed over the pair, in one launch, in place or not, bit for bit
-what :class:`.host.ApplyJonesHost` defines. The classes follow DESIGN.md, "Adding an operation".
+what :class:`.host.ApplyJonesHost` defines. And what joins the two halves of that chain: the
+solved matrices filled whole across the channels the solver lost, per antenna, with a delay
+model per feed, in one launch, bit for bit what :class:`.host.InterpolateJonesHost` defines,
+and the diagonal of the matrices as the gains a delay fit reads
+(:class:`.host.JonesDiagonalHost`). The classes follow DESIGN.md, "Adding an operation".
 """
 
 import ctypes
@@ -1490,6 +1494,253 @@ class InterpolateGainsHostFromDevice:
         given = {"gains": gains, "status": status, "model": model, "scale": scale}
         out = _native_op.run_once(fn, self.command_queue, given, names)
         return tuple(out) + (() if template.normalise else (None,))
+
+
+class InterpolateJonesTemplate(_native_op.NativeTemplate):
+    """The 2x2 counterpart of :class:`InterpolateGainsTemplate`, between
+    :class:`SolveJonesTemplate` (``corrections=False``) and the :class:`ApplyJonesTemplate` of
+    a target scan: per antenna, the solved matrices with a delay model per feed divided out,
+    smoothed, normalised, filled whole across the channels the solver left without a matrix
+    (gaps of at most `max_gap` channels), multiplied by the model and by a band-wide gain per
+    feed again, and inverted; one kernel launch with one workgroup per antenna; see
+    :class:`host.InterpolateJonesHost` for every step. The `model` is what
+    :class:`FitDelaysTemplate` (``corrections=False``) fits to the gains that
+    :class:`JonesDiagonalTemplate` extracts.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    max_gap, smooth, normalise, status_mask, corrections
+        As for :class:`host.InterpolateJonesHost` (same errors)
+    status
+        ``True``: there is a `status` slot (:class:`SolveJones`'s)
+    model
+        ``True``: there is a `model` slot (:class:`FitDelays`'s)
+    scale
+        ``True``: there is a `scale` slot
+    tuning
+        The kernel picks its launch geometry from the shape: nothing to tune, any key is a
+        ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.InterpolateJonesHost
+    KERNEL = "ksp_interpolate_jones"
+
+    def __init__(self, context: AbstractContext, max_gap: int, smooth: int = 1,
+                 normalise: bool = False, status: bool = True, status_mask: int = 0xFF,
+                 model: bool = True, scale: bool = False, corrections: bool = False,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:  # fmt: skip
+        self.checked = host.InterpolateJonesHost(max_gap, smooth, normalise, status_mask,
+                                                 corrections)  # fmt: skip
+        self.max_gap = self.checked.max_gap
+        self.smooth = self.checked.smooth
+        self.normalise = self.checked.normalise
+        self.status = bool(status)
+        self.status_mask = self.checked.status_mask
+        self.model = bool(model)
+        self.scale = bool(scale)
+        self.corrections = self.checked.corrections
+        self._setup(context, tuning)
+
+
+class InterpolateJones(_native_op.NativeOperation):
+    """Concrete :class:`InterpolateJonesTemplate` (``ValueError`` if `channels` is outside
+    1..16384 or `n_inputs` is odd or outside 2..2048).
+
+    .. rubric:: Slots
+
+    **jones** : channels x n_inputs x 2, complex64 (the last axis is not padded)
+    **status** : channels, uint8 (only with ``status``)
+    **model** : channels x n_inputs, complex64 (only with ``model``)
+    **scale** : n_inputs, complex64 (only with ``scale``)
+    **out** : channels x n_inputs x 2, complex64 (the last axis is not padded)
+    **kept** : n_inputs // 2, int32
+    **filled** : n_inputs // 2, int32
+    **fill_status** : n_inputs // 2, uint8
+    **mean_amplitude** : n_inputs // 2, float32 (only with ``normalise``)
+
+    Every padded dimension is an object of its own, so ``jones`` and ``status`` can be
+    compounded with :class:`SolveJones`'s outputs, ``model`` with :class:`FitDelays`'s and
+    ``out`` with :class:`ApplyJones`'s ``jones``, each taking the other's padding. ``out`` may
+    be bound to the buffer of ``jones``: the operation then works in place.
+    """
+
+    def __init__(self, template: InterpolateJonesTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, n_inputs: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, n_inputs, allocator)
+        template.checked.check_shape(channels, n_inputs)
+        self.n_inputs = n_inputs
+
+        def per_antenna(dtype) -> accel.IOSlot:
+            return accel.IOSlot((accel.Dimension(n_inputs // 2),), dtype)
+
+        def matrices() -> accel.IOSlot:
+            return accel.IOSlot((channels, accel.Dimension(n_inputs),
+                                 accel.Dimension(2, exact=True)), np.complex64)  # fmt: skip
+
+        self.slots["jones"] = matrices()
+        if template.status:
+            self.slots["status"] = accel.IOSlot((accel.Dimension(channels),), np.uint8)
+        if template.model:
+            self.slots["model"] = accel.IOSlot((channels, accel.Dimension(n_inputs)),
+                                               np.complex64)  # fmt: skip
+        if template.scale:
+            self.slots["scale"] = accel.IOSlot((accel.Dimension(n_inputs),), np.complex64)
+        self.slots["out"] = matrices()
+        self.slots["kept"] = per_antenna(np.int32)
+        self.slots["filled"] = per_antenna(np.int32)
+        self.slots["fill_status"] = per_antenna(np.uint8)
+        if template.normalise:
+            self.slots["mean_amplitude"] = per_antenna(np.float32)
+
+    def _run(self) -> None:
+        template = self.template
+        jones = self.buffer("jones")
+        status = self.buffer("status") if template.status else None
+        model = self.buffer("model") if template.model else None
+        scale = self.buffer("scale") if template.scale else None
+        out = self.buffer("out")
+        mean_amplitude = self.buffer("mean_amplitude") if template.normalise else None
+        self._launch(
+            jones.buffer,
+            _native_op.pointer(status),
+            _native_op.pointer(model),
+            _native_op.pointer(scale),
+            out.buffer,
+            self.buffer("kept").buffer,
+            self.buffer("filled").buffer,
+            self.buffer("fill_status").buffer,
+            _native_op.pointer(mean_amplitude),
+            np.int32(self.channels),
+            np.int32(self.n_inputs),
+            np.int32(jones.padded_shape[1]),
+            _native_op.stride(model),
+            np.int32(out.padded_shape[1]),
+            np.int32(template.max_gap),
+            np.int32(template.smooth),
+            np.int32(template.status_mask),
+            np.int32(template.corrections),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        template = self.template
+        return {"max_gap": template.max_gap, "smooth": template.smooth,
+                "normalise": template.normalise, "status": template.status,
+                "status_mask": template.status_mask, "model": template.model,
+                "scale": template.scale, "corrections": template.corrections,
+                "channels": self.channels, "n_inputs": self.n_inputs}  # fmt: skip
+
+
+InterpolateJonesTemplate.operation_class = InterpolateJones
+
+
+class InterpolateJonesHostFromDevice:
+    """Make an :class:`InterpolateJonesTemplate` callable like
+    :class:`host.InterpolateJonesHost`: ``(jones, status=None, model=None, scale=None)`` in,
+    ``(out, kept, filled, fill_status, mean_amplitude or None)`` out; allocates on every call.
+    ``TypeError`` unless `status`, `model` and `scale` are given exactly when the template has
+    them."""
+
+    def __init__(self, template: InterpolateJonesTemplate,
+                 command_queue: AbstractCommandQueue) -> None:
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, jones: np.ndarray, status: Optional[np.ndarray] = None,
+                 model: Optional[np.ndarray] = None, scale: Optional[np.ndarray] = None):  # fmt: skip
+        template = self.template
+        _native_op.check_optional(status, template.status, "status")
+        _native_op.check_optional(model, template.model, "model")
+        _native_op.check_optional(scale, template.scale, "scale")
+        channels, n_inputs = np.shape(jones)[:2]
+        fn = template.instantiate(self.command_queue, channels, n_inputs)
+        names = ["out", "kept", "filled", "fill_status"] + (
+            ["mean_amplitude"] if template.normalise else [])  # fmt: skip
+        given = {"jones": jones, "status": status, "model": model, "scale": scale}
+        out = _native_op.run_once(fn, self.command_queue, given, names)
+        return tuple(out) + (() if template.normalise else (None,))
+
+
+class JonesDiagonalTemplate(_native_op.NativeTemplate):
+    """The diagonal of every antenna's 2x2 matrix as per-input gains, ``gains[c, p] = jones[c,
+    p, p % 2]``: what lets :class:`FitDelaysTemplate` fit one delay per feed to the table of
+    :class:`SolveJonesTemplate`; see :class:`host.JonesDiagonalHost`. One kernel launch.
+
+    Parameters
+    ----------
+    context
+        Context whose device will run the kernel
+    tuning
+        Nothing to tune, any key is a ``ValueError`` (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.JonesDiagonalHost
+    KERNEL = "ksp_jones_diagonal"
+
+    def __init__(self, context: AbstractContext,
+                 tuning: Optional[Mapping[str, Any]] = None) -> None:
+        self._setup(context, tuning)
+
+
+class JonesDiagonal(_native_op.NativeOperation):
+    """Concrete :class:`JonesDiagonalTemplate` (``ValueError`` if `channels` or `n_inputs` is
+    below 1).
+
+    .. rubric:: Slots
+
+    **jones** : channels x n_inputs x 2, complex64 (the last axis is not padded)
+    **gains** : channels x n_inputs, complex64
+
+    Every padded dimension is an object of its own: ``jones`` compounds with
+    :class:`SolveJones`'s output and ``gains`` with :class:`FitDelays`'s input.
+    """
+
+    def __init__(self, template: JonesDiagonalTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, n_inputs: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, n_inputs, allocator)
+        if channels < 1:
+            raise ValueError("channels must be at least 1")
+        if n_inputs < 1:
+            raise ValueError("n_inputs must be at least 1")
+        self.n_inputs = n_inputs
+        self.slots["jones"] = accel.IOSlot(
+            (channels, accel.Dimension(n_inputs), accel.Dimension(2, exact=True)), np.complex64)  # fmt: skip
+        self.slots["gains"] = accel.IOSlot((channels, accel.Dimension(n_inputs)), np.complex64)
+
+    def _run(self) -> None:
+        jones, gains = self.buffer("jones"), self.buffer("gains")
+        self._launch(
+            jones.buffer,
+            gains.buffer,
+            np.int32(self.channels),
+            np.int32(self.n_inputs),
+            np.int32(jones.padded_shape[1]),
+            np.int32(gains.padded_shape[1]),
+        )
+
+    def parameters(self) -> Mapping[str, Any]:
+        return {"channels": self.channels, "n_inputs": self.n_inputs}
+
+
+JonesDiagonalTemplate.operation_class = JonesDiagonal
+
+
+class JonesDiagonalHostFromDevice:
+    """Make a :class:`JonesDiagonalTemplate` callable like :class:`host.JonesDiagonalHost`:
+    ``(jones)`` in, ``gains`` out; allocates on every call."""
+
+    def __init__(self, template: JonesDiagonalTemplate,
+                 command_queue: AbstractCommandQueue) -> None:
+        self.template = template
+        self.command_queue = command_queue
+
+    def __call__(self, jones: np.ndarray) -> np.ndarray:
+        channels, n_inputs = np.shape(jones)[:2]
+        fn = self.template.instantiate(self.command_queue, channels, n_inputs)
+        return _native_op.run_once(fn, self.command_queue, {"jones": jones}, ["gains"])[0]
 
 
 class RangePercentilesTemplate(_native_op.NativeTemplate):
