@@ -612,6 +612,33 @@ int ksp_solve_gains(int device, void *stream, const void *vis, const float *weig
                     int pairs_stride, int initial_stride, int gains_stride, int max_iterations,
                     float tol2, int reference, int mask, int corrections);
 
+/* solve_gains_large: ksp_solve_gains for n_inputs 1..512 (bit for bit what rfi/host.py
+ * SolveGainsLargeHost computes: the arithmetic of SolveGainsHost, with up to 16 block sums per
+ * row and in the convergence sums; up to 128 inputs the results are those of ksp_solve_gains).
+ * Every array, stride and setting is as for ksp_solve_gains, with the same rules for an entry
+ * of pairs, the same kept-sample rule and the same status bits.
+ * Above 128 inputs a channel's matrix (12 n_inputs^2 bytes) does not fit LDS and lives in
+ * work_area, device memory the caller supplies: ksp_solve_gains_large_work_bytes(channels,
+ * n_inputs) bytes, 4-byte aligned, sharing no byte with any other argument (all work_bytes of
+ * it count). A fixed grid of G = min(256, channels) workgroups is launched, workgroup i solving
+ * channels i, i + G, ... one after another in slot i of the work area, so
+ *   work bytes = min(256, channels) * 12 * n_inputs * ld,  ld = n_inputs rounded up to 32,
+ * at most 768 MiB (512 inputs, 256 or more channels). A slot is rewritten for every channel
+ * before it is read: the work area need not be cleared, its contents after the call mean
+ * nothing, nothing behind the needed bytes is touched, and it may be shared with anything that
+ * does not run at the same time. The function gives 0 for channels < 1 and for n_inputs outside
+ * 129..512: up to 128 inputs the call is handed to ksp_solve_gains after the checks, and
+ * work_area and work_bytes are not looked at. One kernel launch, no atomics, no workgroup waits
+ * for another. Every argument is checked before any device call. */
+size_t ksp_solve_gains_large_work_bytes(int channels, int n_inputs);
+int ksp_solve_gains_large(int device, void *stream, const void *vis, const float *weights,
+                          const uint8_t *flags, const int32_t *pairs, const void *initial,
+                          void *gains, int32_t *iterations, uint8_t *status, void *work_area,
+                          size_t work_bytes, int channels, int baselines, int n_inputs,
+                          int vis_stride, int weights_stride, int flags_stride, int pairs_stride,
+                          int initial_stride, int gains_stride, int max_iterations, float tol2,
+                          int reference, int mask, int corrections);
+
 /* solve_jones: per-antenna 2x2 Jones matrices solved per channel from averaged visibilities of
  * an unpolarised unit source at the phase centre, with the full-polarisation StEFCal step, in
  * one launch (no reference counterpart; bit for bit what rfi/host.py SolveJonesHost computes,

@@ -202,6 +202,11 @@ SIGNATURES = {
         c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
         c_int, c_int, c_int,
     ],
+    "ksp_solve_gains_large": [
+        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+        c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+        c_int, c_int, c_float, c_int, c_int, c_int,
+    ],
     "ksp_solve_jones": [
         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
         c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
@@ -249,6 +254,7 @@ _OTHER = {
     "ksp_abi_version": ([], c_int),
     "ksp_last_error": ([], c_char_p),
     "ksp_band_average_work_bytes": ([c_int, c_int, c_int], c_size_t),
+    "ksp_solve_gains_large_work_bytes": ([c_int, c_int], c_size_t),
 }
 
 #: functions whose int return value is a result, not an error code

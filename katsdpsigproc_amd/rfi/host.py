@@ -807,8 +807,8 @@ class SolveGainsHost:
 
     @classmethod
     def check_n_inputs(cls, n_inputs) -> int:
-        """`n_inputs` as an int in 1..128 (``ValueError`` otherwise, ``TypeError`` for a value
-        that is not an integer)."""
+        """`n_inputs` as an int in 1..:attr:`MAX_INPUTS` (``ValueError`` otherwise,
+        ``TypeError`` for a value that is not an integer)."""
         if isinstance(n_inputs, (bool, np.bool_)) or not isinstance(n_inputs, (int, np.integer)):
             raise TypeError(f"n_inputs {n_inputs!r} is not an integer")
         if not 1 <= n_inputs <= cls.MAX_INPUTS:
@@ -858,12 +858,13 @@ class SolveGainsHost:
         (n_inputs, n_inputs), optional float32 `weights`, optional uint8 `flags` (both channels,
         baselines) and optional complex64 `initial` (channels, n_inputs). ``ValueError``, naming
         the argument, for a wrong dtype, rank or shape (channels and baselines at least 1,
-        n_inputs 1..128) and for a `reference` that is not below n_inputs. No argument is
-        modified."""
+        n_inputs 1..:attr:`MAX_INPUTS`) and for a `reference` that is not below n_inputs. No
+        argument is modified."""
         vis = _check_array("vis", vis, np.complex64, "(channels, baselines)",
                            lambda s: len(s) == 2 and s[0] >= 1 and s[1] >= 1)  # fmt: skip
         channels, baselines = vis.shape
-        pairs = _check_array("pairs", pairs, np.int32, "(n_inputs, n_inputs), n_inputs 1..128",
+        pairs = _check_array("pairs", pairs, np.int32,
+                             f"(n_inputs, n_inputs), n_inputs 1..{self.MAX_INPUTS}",
                              lambda s: len(s) == 2 and s[0] == s[1]
                              and 1 <= s[0] <= self.MAX_INPUTS)  # fmt: skip
         n = pairs.shape[0]
@@ -983,6 +984,17 @@ class SolveGainsHost:
             gains.imag[...] = np.where(has, g_im, f32(np.nan))
             assert g_re.dtype == f32 and g_im.dtype == f32
         return gains, iterations, status
+
+
+class SolveGainsLargeHost(SolveGainsHost):
+    """:class:`SolveGainsHost` for up to 512 inputs: the same arguments, ``pair_table``,
+    arithmetic and results, with up to 16 block sums of :attr:`BLOCK` = 32 indices per row and
+    in the convergence sums instead of 4. Up to 128 inputs the results are bit for bit those of
+    :class:`SolveGainsHost`. No reference counterpart; this class is the definition that the
+    device operation (:class:`.ingest.SolveGainsLargeTemplate`) matches bit for bit."""
+
+    MAX_INPUTS = 512
+    _CHUNK = 8  # (a channel's three matrices are 3 MiB at 512 inputs)
 
 
 class SolveJonesHost(SolveGainsHost):

@@ -18,7 +18,9 @@ between averaging and the consumers of calibrated data: per-input gain correctio
 ``vis``, ``weights`` and ``flags`` in one launch, in place or not, bit for bit what
 :class:`.host.ApplyGainsHost` defines. And what produces those gains: per channel, the
 per-input gains of a point source solved with StEFCal in one launch, one workgroup per channel,
-bit for bit what :class:`.host.SolveGainsHost` defines. And the step in front of that for a field
+bit for bit what :class:`.host.SolveGainsHost` defines (for arrays of up to 512 inputs, with the
+matrices in a work area: :class:`.host.SolveGainsLargeHost`). And the step in front of that for a
+field
 that is not one source at the phase centre: the model visibilities of up to 64 point sources,
 with float64 phases, and optionally the data divided by them, in one launch, bit for bit what
 :class:`.host.PredictHost` defines. And the step behind the solver: per input, the delay and
@@ -549,7 +551,7 @@ class SolveGainsTemplate(_native_op.NativeTemplate):
         self.weights = bool(weights)
         self.flags = bool(flags)
         self.initial = bool(initial)
-        checked = host.SolveGainsHost(max_iterations, tol, reference, mask, corrections)
+        checked = self.host_class(max_iterations, tol, reference, mask, corrections)
         self.max_iterations = checked.max_iterations
         self.tol = checked.tol
         self.tol2 = checked.tol2
@@ -586,7 +588,7 @@ class SolveGains(_native_op.NativeOperation):
         super().__init__(template, command_queue, channels, baselines, allocator)
         if channels < 1 or baselines < 1:
             raise ValueError("channels and baselines must be at least 1")
-        self.n_inputs = host.SolveGainsHost.check_n_inputs(n_inputs)
+        self.n_inputs = template.host_class.check_n_inputs(n_inputs)
         if template.reference >= n_inputs:
             raise ValueError(f"reference must be -1 or 0..n_inputs-1 = {n_inputs - 1}, "
                              f"not {template.reference}")  # fmt: skip
@@ -610,13 +612,14 @@ class SolveGains(_native_op.NativeOperation):
         self.slots["iterations"] = accel.IOSlot((accel.Dimension(channels),), np.int32)
         self.slots["status"] = accel.IOSlot((accel.Dimension(channels),), np.uint8)
 
-    def _run(self) -> None:
+    def _arguments(self) -> list:
+        """The arguments of ``ksp_solve_gains`` after ``(device, stream)``."""
         template = self.template
         vis, pairs, gains = self.buffer("vis"), self.buffer("pairs"), self.buffer("gains")
         weights = self.buffer("weights") if template.weights else None
         flags = self.buffer("flags") if template.flags else None
         initial = self.buffer("initial") if template.initial else None
-        self._launch(
+        return [
             vis.buffer,
             _native_op.pointer(weights),
             _native_op.pointer(flags),
@@ -639,7 +642,10 @@ class SolveGains(_native_op.NativeOperation):
             np.int32(template.reference),
             np.int32(template.mask),
             np.int32(template.corrections),
-        )
+        ]
+
+    def _run(self) -> None:
+        self._launch(*self._arguments())
 
     def parameters(self) -> Mapping[str, Any]:
         template = self.template
@@ -677,13 +683,93 @@ class SolveGainsHostFromDevice:
         if np.shape(inputs) != (baselines, 2):
             raise ValueError(f"inputs must have shape (baselines, 2) = ({baselines}, 2), "
                              f"not {np.shape(inputs)}")  # fmt: skip
-        pairs = host.SolveGainsHost.pair_table(inputs, n_inputs)
+        pairs = template.host_class.pair_table(inputs, n_inputs)
         fn = template.instantiate(self.command_queue, channels, baselines, n_inputs)
         given = {"vis": vis, "pairs": pairs, "weights": weights, "flags": flags,
                  "initial": initial}  # fmt: skip
         out = _native_op.run_once(fn, self.command_queue, given,
                                   ["gains", "iterations", "status"])  # fmt: skip
         return out[0], out[1], out[2]
+
+
+class SolveGainsLargeTemplate(SolveGainsTemplate):
+    """:class:`SolveGainsTemplate` for arrays of up to 512 inputs, with the same parameters
+    (same errors, `reference` up to 511) and the same results; see
+    :class:`host.SolveGainsLargeHost`. Above 128 inputs a channel's matrix does not fit LDS:
+    a fixed grid of :attr:`SolveGainsLarge.WORKGROUPS` workgroups solves the channels one after
+    another, each with its matrix in its own part of a work area in device memory. Up to 128
+    inputs the operation is :class:`SolveGains` under another name: the same launcher, no work
+    area.
+
+    Parameters
+    ----------
+    tuning
+        The launch geometry is fixed: nothing to tune, any key is a ``ValueError``
+        (:func:`.tune.fixed_geometry`).
+    """
+
+    host_class = host.SolveGainsLargeHost
+    KERNEL = "ksp_solve_gains_large"
+    SMALL_KERNEL = SolveGainsTemplate.KERNEL
+
+    def _setup(self, context: AbstractContext, tuning: Optional[Mapping[str, Any]]) -> None:
+        super()._setup(context, tuning)
+        self.small_kernel = context.native_kernel(self.SMALL_KERNEL)
+
+
+class SolveGainsLarge(SolveGains):
+    """Concrete :class:`SolveGainsLargeTemplate` (``ValueError`` if `channels` or `baselines`
+    is below 1, `n_inputs` outside 1..512 or the template's `reference` not below `n_inputs`).
+
+    .. rubric:: Slots
+
+    Those of :class:`SolveGains`, which compound in the same way, and for `n_inputs` above 128
+
+    **work_area** : :meth:`work_bytes` scratch bytes for the channels' matrices; exposed so
+    that several operations that do not run at once can share one allocation (it need not be
+    cleared)
+
+    Up to 128 inputs there is no such slot and the launcher is that of :class:`SolveGains`.
+    """
+
+    #: the most inputs whose matrix the kernel of :class:`SolveGains` keeps in LDS
+    SMALL_INPUTS = host.SolveGainsHost.MAX_INPUTS
+    #: workgroups launched at most (``SGL_WORKGROUPS``): the parts of the work area
+    WORKGROUPS = 256
+
+    def __init__(self, template: SolveGainsLargeTemplate, command_queue: AbstractCommandQueue,
+                 channels: int, baselines: int, n_inputs: int,
+                 allocator: Optional[AbstractAllocator] = None) -> None:  # fmt: skip
+        super().__init__(template, command_queue, channels, baselines, n_inputs, allocator)
+        if self.n_inputs > self.SMALL_INPUTS:
+            self.slots["work_area"] = accel.IOSlot(
+                (accel.Dimension(self.work_bytes(channels, n_inputs), exact=True),), np.uint8)  # fmt: skip
+
+    @classmethod
+    def work_bytes(cls, channels: int, n_inputs: int) -> int:
+        """What ``ksp_solve_gains_large_work_bytes`` returns: for each of ``min(WORKGROUPS,
+        channels)`` workgroups three float32 planes of `n_inputs` rows of `n_inputs` rounded up
+        to 32 elements, at most 768 MiB; 0 up to 128 inputs and out of range."""
+        if channels < 1 or not cls.SMALL_INPUTS < n_inputs <= host.SolveGainsLargeHost.MAX_INPUTS:
+            return 0
+        row = -(-n_inputs // 32) * 32
+        return min(cls.WORKGROUPS, channels) * 3 * n_inputs * row * 4
+
+    def _run(self) -> None:
+        args = self._arguments()
+        if self.n_inputs <= self.SMALL_INPUTS:
+            self.command_queue.enqueue_kernel(self.template.small_kernel, args)
+            return
+        work = self.buffer("work_area")
+        self._launch(*args[:8], work.buffer, np.uint64(work.shape[0]), *args[8:])
+
+
+SolveGainsLargeTemplate.operation_class = SolveGainsLarge
+
+
+class SolveGainsLargeHostFromDevice(SolveGainsHostFromDevice):
+    """:class:`SolveGainsHostFromDevice` for a :class:`SolveGainsLargeTemplate`: the same
+    arguments and results, `n_inputs` up to 512."""
 
 
 class SolveJonesTemplate(_native_op.NativeTemplate):
